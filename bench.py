@@ -23,7 +23,15 @@ has no host work; the K timed steps are replayed from HIP graphs of one
 episode (100 steps) each; when N > 1 the ranks' shards need no exchange,
 and the RCCL all-reduce of the episode metrics runs after the timed region.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, settles and warms up, times the K steps and prints the
+line. `--full` adds what takes runs of its own after the timed region: the
+device time of one more timed graph (`timed_region.graph_device_us` and the
+figures derived from it), the per-kernel roofline and the CPU baseline
+(`--no-kernel-timing` / `--no-cpu-baseline` leave one out); without it those
+keys are null or absent. `--dump-outputs DIR` writes the env's outputs of
+the last timed step as DIR/<name>.npy (dump_outputs below).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...
 Prints ONE JSON line on rank 0 (diagnostics go to stderr).
 """
@@ -344,6 +352,40 @@ def pmc_entry(key):
     return (e, "ok") if e else (None, f"no PMC entry for {key}")
 
 
+DUMP_BUDGET = 60 << 20   # bytes of all dumped arrays together (under the 64 MB a dump may take)
+
+
+def dump_outputs(out_dir, outs, prefix=""):
+    """Write the device tensors `outs` (name -> tensor) as out_dir/<prefix><name>.npy.
+
+    float32, or float64 for float64 data and for integers that float32 cannot
+    hold exactly (|x| >= 2^24). The arrays share DUMP_BUDGET bytes, smallest
+    first, each taking at most an equal share of what is left: one that does
+    not fit is written as a fixed sample of its flattened elements (sorted
+    indices drawn without replacement from numpy's default_rng(0), the same
+    for every run of the same shape)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    for name, t in outs.items():
+        a = t.detach().cpu().numpy()
+        wide = a.dtype == np.float64 or (a.dtype.kind in "iu" and a.size > 0 and
+                                         max(abs(int(a.min())), abs(int(a.max()))) >= 1 << 24)
+        arrs[name] = np.ascontiguousarray(a, dtype=np.float64 if wide else np.float32)
+    left = DUMP_BUDGET
+    order = sorted(arrs, key=lambda k: (arrs[k].nbytes, k))
+    for i, name in enumerate(order):
+        a = arrs[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            log(f"dump: {name} {a.shape} sampled to {n} of {a.size} elements")
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        left -= a.nbytes
+        np.save(out_dir / f"{prefix}{name}.npy", a)
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -365,12 +407,18 @@ def parse_args(argv=None):
                     help="BASELINE config (h = 24 agents x 8192 envs per GPU)")
     ap.add_argument("--n-agents", type=int, default=None, help="override the config's agents")
     ap.add_argument("--n-envs", type=int, default=None, help="override the config's envs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what takes runs of its own: the device time of "
+                         "one more timed graph, the per-kernel roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the env's outputs of the last timed step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; rank r > 0 of a multi-GPU run as rank<r>_<name>.npy)")
     ap.add_argument("--kernel-launches", type=int, default=100,
-                    help="back-to-back launches per kernel for the event-timed roofline")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+                    help="--full: back-to-back launches per kernel for the event-timed roofline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: seconds of the CPU baseline")
     ap.add_argument("--cpu-cores", type=int, default=0, help="host processes for the CPU baseline (0: all, <= 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the roofline timing (null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (null)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the roofline timing (null)")
     ap.add_argument("--settle-ms", type=float, default=20.0,
                     help="before the warmup, whole untimed episodes (EL steps each, so the alignment holds) "
                          "until this much wall time has passed with the GPU busy: clocks at their loaded level "
@@ -719,6 +767,10 @@ def run_rank(args):
             run_steps(EL, 3)
             settle_steps += EL
             sync()
+        # the settle count depends on the clock: start again from the seeded
+        # layout (as after the reset above), so that the warmup and the timed
+        # steps see the same states in every run of the same arguments
+        env.reset(seed=cfg.seed, sync_edges=False)
         if A > 0 and a_slot == 3:   # (slot 1 holds the remainder graph)
             capture(A, 3)
     for _ in range(W // EL if buf is not None else 0):
@@ -794,6 +846,12 @@ def run_rank(args):
         if pg:
             dist.destroy_process_group()
         return 3
+    if args.dump_outputs and not stub:
+        # what a caller of the timed path holds after its last step: the env's
+        # output tensors (--buffer: the episode's last slot), before anything
+        # below steps the env again
+        dump_outputs(args.dump_outputs, buf.slot(EL) if buf is not None else env.outputs(),
+                     f"rank{rank}_" if rank else "")
     # the episode metrics over all ranks: the RCCL all-reduce (after the
     # timed region, see there)
     metrics.copy_(env.episode_metrics())
@@ -820,7 +878,7 @@ def run_rank(args):
     # graph — against K x the settled per-step time of back-to-back launches
     # of the roofline's timing below
     graph_us = None
-    if not eager and not stub:
+    if args.full and not eager and not stub:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         sync()
         run_steps(chunk, 0)
@@ -832,11 +890,11 @@ def run_rank(args):
         graph_us = e0.elapsed_time(e1) * 1e3
 
     roofline = None
-    if not args.no_kernel_timing and not eager and not stub:
+    if args.full and not args.no_kernel_timing and not eager and not stub:
         roofline = kernel_roofline(env, cfg, actions, args, N, B, EL, roll, buf)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
         cpu = cpu_baseline(cfg, args.cpu_seconds, args.cpu_cores or host_cores())
 
     if rank == 0:

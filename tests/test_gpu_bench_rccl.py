@@ -25,7 +25,7 @@ def test_bench_rank_body_over_rccl_one_rank():
         env.pop(k, None)
     env["MASTER_ADDR"] = "127.0.0.1"
     r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--settle-ms", "20", "--force-pg"],
+                        "--full", "--no-cpu-baseline", "--settle-ms", "20", "--force-pg"],
                        capture_output=True, text=True, timeout=100, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

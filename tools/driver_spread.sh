@@ -6,8 +6,8 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; T=$1; R=${2:-6}
 O=gpurun_out/$T; mkdir -p $O
 for i in $(seq 1 $R); do
-  timeout -k 10 120 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/plain_$i.json 2> $O/plain_$i.err || exit 1
-  timeout -k 10 120 taskset -c 3 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/pin_$i.json 2> $O/pin_$i.err || exit 1
+  timeout -k 10 120 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/plain_$i.json 2> $O/plain_$i.err || exit 1
+  timeout -k 10 120 taskset -c 3 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/pin_$i.json 2> $O/pin_$i.err || exit 1
 done
 python3 - $O <<'PY'
 import json, glob, sys

@@ -21,8 +21,10 @@ CMD=$1; T=$2; shift 2
 O=gpurun_out/$T
 mkdir -p $O
 
-# bench arguments of a named line
-line_args() {
+# bench arguments of a named line: --full (the roofline, graph split and CPU
+# baseline figures the lines are read for) + the line's own
+line_args() { local a; a=$(line_own_args $1) || return 1; echo "--full $a"; }
+line_own_args() {
   case $1 in
     h) echo "" ;;
     driver) echo "--gpus 1 --steps 20 --warmup 5" ;;
