@@ -1431,18 +1431,83 @@ int gsm_graph_kernel_ms(gsm_handle *h, int32_t slot, float *step_ms, float *emit
     return GSM_OK;
 }
 
-int gsm_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w, const float *w_e,
-                       const int64_t *row_ptr, const int32_t *col, const float *skip, int64_t n_nodes,
-                       int32_t heads, int32_t channels, float scale, float *out, void *stream) {
+static int attn_forward(const float *q, const float *k, const float *v, const float *edge_w, const float *w_e,
+                        const int64_t *row_ptr, const int32_t *col, const float *skip, int64_t n_nodes,
+                        int32_t heads, int32_t channels, float scale, float *out, float *lse, bool want_lse,
+                        void *stream, const char *what) {
     if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 40)) return fail(nullptr, GSM_EINVAL, "bad n_nodes");
     if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
         return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
     if (n_nodes == 0) return GSM_OK;
-    if (!q || !k || !v || !row_ptr || !col || !out) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    if (!q || !k || !v || !row_ptr || !col || !out || (want_lse && !lse))
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
     if (!!edge_w != !!w_e) return fail(nullptr, GSM_EINVAL, "edge_w and w_e go together");
     const hipError_t e = gsm::launch_attn_aggregate(q, k, v, edge_w, w_e, row_ptr, col, skip, n_nodes,
-                                                    heads * channels, channels, scale, out, as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_attn_aggregate launch");
+                                                    heads * channels, channels, scale, out, lse,
+                                                    as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, what);
+    return GSM_OK;
+}
+
+int gsm_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w, const float *w_e,
+                       const int64_t *row_ptr, const int32_t *col, const float *skip, int64_t n_nodes,
+                       int32_t heads, int32_t channels, float scale, float *out, void *stream) {
+    return attn_forward(q, k, v, edge_w, w_e, row_ptr, col, skip, n_nodes, heads, channels, scale, out, nullptr,
+                        false, stream, "gsm_attn_aggregate launch");
+}
+
+int gsm_attn_aggregate_fwd(const float *q, const float *k, const float *v, const float *edge_w,
+                           const float *w_e, const int64_t *row_ptr, const int32_t *col, const float *skip,
+                           int64_t n_nodes, int32_t heads, int32_t channels, float scale, float *out, float *lse,
+                           void *stream) {
+    return attn_forward(q, k, v, edge_w, w_e, row_ptr, col, skip, n_nodes, heads, channels, scale, out, lse,
+                        true, stream, "gsm_attn_aggregate_fwd launch");
+}
+
+int gsm_attn_backward_work_floats(int64_t n_nodes, int64_t n_edges, int32_t heads, int32_t channels,
+                                  int64_t *n_floats) {
+    if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 40)) return fail(nullptr, GSM_EINVAL, "bad n_nodes");
+    if (n_edges < 0 || n_edges >= ((int64_t)1 << 31)) return fail(nullptr, GSM_EINVAL, "bad n_edges");
+    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
+        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
+    *n_floats = gsm::attn_backward_work_floats(n_edges, heads, heads * channels);
+    return GSM_OK;
+}
+
+int gsm_attn_aggregate_bwd(const float *grad_out, const float *q, const float *k, const float *v,
+                           const float *edge_w, const float *w_e, const int64_t *row_ptr, const int32_t *col,
+                           const float *out, const float *skip, const float *lse, const int64_t *t_ptr,
+                           const int32_t *t_edge, const int32_t *t_tgt, int64_t n_nodes, int64_t n_edges,
+                           int32_t heads, int32_t channels, float scale, float *work, float *dq, float *dk,
+                           float *dv, float *dedge_w, float *dw_e, void *stream) {
+    if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 40)) return fail(nullptr, GSM_EINVAL, "bad n_nodes");
+    if (n_edges < 0 || n_edges >= ((int64_t)1 << 31)) return fail(nullptr, GSM_EINVAL, "bad n_edges");
+    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
+        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (n_nodes == 0 && n_edges > 0) return fail(nullptr, GSM_EINVAL, "edges without nodes");
+    if (!!edge_w != !!w_e) return fail(nullptr, GSM_EINVAL, "edge_w and w_e go together");
+    if (dedge_w && !edge_w) return fail(nullptr, GSM_EINVAL, "dedge_w needs edge_w");
+    hipStream_t s = as_stream(stream);
+    const size_t row = sizeof(float) * (size_t)(heads * channels);
+    hipError_t e = hipSuccess;
+    if (n_nodes == 0 || n_edges == 0) {
+        // no edges: every gradient but dskip (= grad_out, the caller's) is 0
+        if (n_nodes > 0 && (!dq || !dk || !dv)) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+        if (n_nodes > 0) e = hipMemsetAsync(dq, 0, row * (size_t)n_nodes, s);
+        if (n_nodes > 0 && e == hipSuccess) e = hipMemsetAsync(dk, 0, row * (size_t)n_nodes, s);
+        if (n_nodes > 0 && e == hipSuccess) e = hipMemsetAsync(dv, 0, row * (size_t)n_nodes, s);
+        if (dw_e && e == hipSuccess) e = hipMemsetAsync(dw_e, 0, row, s);
+        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_attn_aggregate_bwd memset");
+        return GSM_OK;
+    }
+    if (!grad_out || !q || !k || !v || !row_ptr || !col || !out || !lse || !t_ptr || !t_edge || !t_tgt || !work ||
+        !dq || !dk || !dv)
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    e = gsm::launch_attn_backward(grad_out, q, k, v, edge_w, w_e, row_ptr, col, out, skip, lse, t_ptr, t_edge,
+                                  t_tgt, n_nodes, n_edges, heads * channels, channels, scale, work, dq, dk, dv,
+                                  dedge_w, dw_e, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_attn_aggregate_bwd launch");
     return GSM_OK;
 }
 

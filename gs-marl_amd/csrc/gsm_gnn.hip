@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void gsm_attn_aggregate_kernel(
     const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
     const float *__restrict__ edge_w, const float *__restrict__ w_e, const int64_t *__restrict__ row_ptr,
     const int32_t *__restrict__ col, const float *__restrict__ skip, int64_t n_nodes, int HC, int C,
-    float scale, float *__restrict__ out) {
+    float scale, float *__restrict__ out, float *__restrict__ lse) {
     using V = VecT<kVec>;
     using T = typename V::T;
     constexpr int kNPW = kWave / kLP;                       // nodes per wave
@@ -126,13 +126,16 @@ __global__ __launch_bounds__(256) void gsm_attn_aggregate_kernel(
         for (int i = 0; i < kVec; ++i)
             V::set(r, i, V::get(acc, i) * inv + (skip ? V::get(sk, i) : 0.0f));
         *(T *)(out + nd * HC + ch) = r;
+        // softmax statistics for the backward: each head's first lane; an
+        // empty row stores a finite value that is never read
+        if (lse && ch % C == 0) lse[nd * (HC / C) + ch / C] = den > 0.0f ? mx + logf(den) : 0.0f;
     }
 }
 
 hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w,
                                  const float *w_e, const int64_t *row_ptr, const int32_t *col,
                                  const float *skip, int64_t n_nodes, int HC, int C, float scale, float *out,
-                                 hipStream_t s) {
+                                 float *lse, hipStream_t s) {
     // four channels per lane (16-byte gathers) when every head spans whole
     // lanes and the rows are 16-byte aligned; one channel per lane otherwise
     const bool vec4 = C % 4 == 0 && HC % 4 == 0 && ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v |
@@ -148,7 +151,7 @@ hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v,
     (void)hipGetLastError();
 #define GSM_ATTN(LP, VEC)                                                                                \
     gsm_attn_aggregate_kernel<LP, VEC><<<blocks, 256, 0, s>>>(q, k, v, edge_w, w_e, row_ptr, col, skip, \
-                                                              n_nodes, HC, C, scale, out)
+                                                              n_nodes, HC, C, scale, out, lse)
     if (vec4) {
         switch (lp) {
             case 1: GSM_ATTN(1, 4); break;
@@ -171,6 +174,302 @@ hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v,
         }
     }
 #undef GSM_ATTN
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Backward. With m_ij = v_j + e_ij, g_i the upstream gradient of out_i:
+//
+//   D_i[h]   = <g_i[h], out_i[h] - skip_i[h]>       (= sum_j a_ij <g_i[h], m_ij[h]>)
+//   ds_ij[h] = a_ij[h] * (<g_i[h], m_ij[h]> - D_i[h])
+//   dq_i[h]  = scale * sum_j ds_ij[h] (k_j[h] + e_ij[h])
+//   dk_j[h]  = scale * sum_{i: j in row i} ds_ij[h] q_i[h]
+//   dv_j[h]  =         sum_{i: j in row i} a_ij[h]  g_i[h]
+//   de_ij[c] = scale * ds_ij[h(c)] q_i[c] + a_ij[h(c)] g_i[c]
+//   dw_e[c]  = sum_ij w_ij de_ij[c],   dedge_w_ij = sum_c de_ij[c] w_e[c]
+//
+// Two gather kernels and no float atomics, so every output is bitwise
+// reproducible. The target kernel walks the CSR rows exactly as the forward
+// does (same lanes-per-node mapping, one-edge-ahead index prefetch), rebuilds
+// a_ij = exp(s_ij - lse_i) from the saved statistics, keeps dq_i in registers
+// and stores a_ij, ds_ij per (entry, head). The source kernel walks the
+// transposed lists (entries grouped by source) and sums dk_j, dv_j in
+// registers from those two arrays and the q / g rows of the entries' targets.
+// dw_e regroups to one [HC] row per node, scale*q_i*U_i + g_i*A_i with
+// U_i = sum_j w_ij ds_ij and A_i = sum_j w_ij a_ij; a block sums the rows of
+// its nodes in a fixed order (registers across its node groups, then LDS) to
+// one partial, and a one-block launch sums the partials in index order.
+
+// target-kernel grid cap = dw_e partial rows: 5 blocks (its occupancy at 96
+// VGPRs) on each of the 256 CUs, so every block is resident from the start and
+// the count, hence the summation order, is the same on every device
+constexpr int kBwdMaxBlocks = 1280;
+constexpr int kBwdSumRows = 16;       // row groups of the dw_e partial sum
+
+template <int kLP, int kVec>
+__global__ __launch_bounds__(256) void gsm_attn_bwd_target_kernel(
+    const float *__restrict__ g, const float *__restrict__ q, const float *__restrict__ k,
+    const float *__restrict__ v, const float *__restrict__ edge_w, const float *__restrict__ w_e,
+    const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col, const float *__restrict__ out,
+    const float *__restrict__ skip, const float *__restrict__ lse, int64_t n_nodes, int64_t n_groups, int HC,
+    int C, float scale, float *__restrict__ wa, float *__restrict__ wds, float *__restrict__ part,
+    float *__restrict__ dq, float *__restrict__ dedge_w) {
+    using V = VecT<kVec>;
+    using T = typename V::T;
+    constexpr int kNPW = kWave / kLP;                       // nodes per wave
+    __shared__ float red[256 * kVec];
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / kLP, ch = (lane % kLP) * kVec;
+    const int lanes_per_head = C / kVec;                    // power of two
+    const int H = HC / C, head = ch < HC ? ch / C : 0;
+    T we, dwe;
+    for (int i = 0; i < kVec; ++i) {
+        V::set(we, i, 0.0f);
+        V::set(dwe, i, 0.0f);
+    }
+    if (ch < HC && w_e) we = *(const T *)(w_e + ch);
+    for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int64_t node = (grp * 4 + (threadIdx.x >> 6)) * kNPW + sub;
+        const bool live = node < n_nodes && ch < HC;
+        const int64_t nd = node < n_nodes ? node : 0;
+        T qi, gi, acc;
+        for (int i = 0; i < kVec; ++i) {
+            V::set(qi, i, 0.0f);
+            V::set(gi, i, 0.0f);
+            V::set(acc, i, 0.0f);
+        }
+        float D = 0.0f, ls = 0.0f;
+        if (live) {
+            qi = *(const T *)(q + nd * HC + ch);
+            gi = *(const T *)(g + nd * HC + ch);
+            T om = *(const T *)(out + nd * HC + ch);
+            if (skip) {
+                const T sk = *(const T *)(skip + nd * HC + ch);
+                for (int i = 0; i < kVec; ++i) V::set(om, i, V::get(om, i) - V::get(sk, i));
+            }
+#pragma unroll
+            for (int i = 0; i < kVec; ++i) D += V::get(gi, i) * V::get(om, i);
+            ls = lse[nd * H + head];
+        }
+#pragma unroll
+        for (int o = 1; o < kLP; o <<= 1)
+            if (o < lanes_per_head) D += __shfl_xor(D, o);
+        // this lane's share of <q_i, w_e> and <g_i, w_e> (dedge_w)
+        float pq = 0.0f, pg = 0.0f;
+#pragma unroll
+        for (int i = 0; i < kVec; ++i) {
+            pq += V::get(qi, i) * V::get(we, i);
+            pg += V::get(gi, i) * V::get(we, i);
+        }
+        const int64_t r0 = node < n_nodes ? row_ptr[nd] : 0, r1 = node < n_nodes ? row_ptr[nd + 1] : 0;
+        const int deg = (int)(r1 - r0);
+        int wdeg = deg;                                      // the wave runs its longest row
+#pragma unroll
+        for (int o = kLP; o < kWave; o <<= 1) wdeg = max(wdeg, __shfl_xor(wdeg, o));
+        float U = 0.0f, A = 0.0f;
+        int64_t jn = (live && deg > 0) ? col[r0] : 0;
+        float wn = (live && deg > 0 && edge_w) ? edge_w[r0] : 0.0f;
+        for (int t = 0; t < wdeg; ++t) {
+            const bool on = live && t < deg;
+            const int64_t j = jn;
+            const float w = wn;
+            if (live && t + 1 < deg) {
+                jn = col[r0 + t + 1];
+                if (edge_w) wn = edge_w[r0 + t + 1];
+            }
+            T kj, vj;
+            for (int i = 0; i < kVec; ++i) {
+                V::set(kj, i, 0.0f);
+                V::set(vj, i, 0.0f);
+            }
+            if (on) {
+                kj = *(const T *)(k + j * HC + ch);
+                vj = *(const T *)(v + j * HC + ch);
+            }
+            float sc = 0.0f, gm = 0.0f;
+#pragma unroll
+            for (int i = 0; i < kVec; ++i) {
+                sc += V::get(qi, i) * (V::get(kj, i) + w * V::get(we, i));
+                gm += V::get(gi, i) * (V::get(vj, i) + w * V::get(we, i));
+            }
+#pragma unroll
+            for (int o = 1; o < kLP; o <<= 1)
+                if (o < lanes_per_head) {
+                    sc += __shfl_xor(sc, o);
+                    gm += __shfl_xor(gm, o);
+                }
+            sc *= scale;
+            const float a = on ? __expf(sc - ls) : 0.0f;
+            const float ds = a * (gm - D);
+#pragma unroll
+            for (int i = 0; i < kVec; ++i)
+                V::set(acc, i, V::get(acc, i) + ds * (V::get(kj, i) + w * V::get(we, i)));
+            U += w * ds;
+            A += w * a;
+            if (on && ch % C == 0) {
+                wa[(r0 + t) * H + head] = a;
+                wds[(r0 + t) * H + head] = ds;
+            }
+            if (dedge_w) {
+                float p = scale * ds * pq + a * pg;
+#pragma unroll
+                for (int o = 1; o < kLP; o <<= 1) p += __shfl_xor(p, o);
+                if (on && ch == 0) dedge_w[r0 + t] = p;
+            }
+        }
+        if (live) {
+            T r;
+#pragma unroll
+            for (int i = 0; i < kVec; ++i) {
+                V::set(r, i, V::get(acc, i) * scale);
+                V::set(dwe, i, V::get(dwe, i) + (scale * V::get(qi, i) * U + V::get(gi, i) * A));
+            }
+            *(T *)(dq + nd * HC + ch) = r;
+        }
+    }
+    if (part) {
+        // the block's dw_e rows -> one partial, summed in slot order
+#pragma unroll
+        for (int i = 0; i < kVec; ++i) red[threadIdx.x * kVec + i] = V::get(dwe, i);
+        __syncthreads();
+        const int c = threadIdx.x;
+        if (c < HC) {
+            float sum = 0.0f;
+            for (int s = 0; s < 256 / kLP; ++s) sum += red[(s * kLP + c / kVec) * kVec + c % kVec];
+            part[(int64_t)blockIdx.x * HC + c] = sum;
+        }
+    }
+}
+
+// one block of 64 * kBwdSumRows threads: row group r sums partials r, r+R, ..
+// in order, then channel c's thread sums the R row groups in order
+__global__ __launch_bounds__(64 * kBwdSumRows) void gsm_attn_bwd_dwe_kernel(const float *__restrict__ part,
+                                                                            int n_part, int HC,
+                                                                            float *__restrict__ dw_e) {
+    __shared__ float red[kBwdSumRows][64];
+    const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
+    float sum = 0.0f;
+    if (c < HC)
+        for (int b = r; b < n_part; b += 8 * kBwdSumRows) {
+            float x[8];                                    // eight loads in flight, added in order
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int bu = b + u * kBwdSumRows;
+                x[u] = bu < n_part ? part[(int64_t)bu * HC + c] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sum += x[u];
+        }
+    red[r][c] = sum;
+    __syncthreads();
+    if (r == 0 && c < HC) {
+        float tot = 0.0f;
+        for (int i = 0; i < kBwdSumRows; ++i) tot += red[i][c];
+        dw_e[c] = tot;
+    }
+}
+
+template <int kLP, int kVec>
+__global__ __launch_bounds__(256) void gsm_attn_bwd_source_kernel(
+    const float *__restrict__ g, const float *__restrict__ q, const float *__restrict__ wa,
+    const float *__restrict__ wds, const int64_t *__restrict__ t_ptr, const int32_t *__restrict__ t_edge,
+    const int32_t *__restrict__ t_tgt, int64_t n_nodes, int HC, int C, float scale, float *__restrict__ dk,
+    float *__restrict__ dv) {
+    using V = VecT<kVec>;
+    using T = typename V::T;
+    constexpr int kNPW = kWave / kLP;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / kLP, ch = (lane % kLP) * kVec;
+    const int64_t node = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * kNPW + sub;
+    if (node >= n_nodes || ch >= HC) return;                // no cross-lane traffic in this kernel
+    const int H = HC / C, head = ch / C;
+    T ak, av;
+    for (int i = 0; i < kVec; ++i) {
+        V::set(ak, i, 0.0f);
+        V::set(av, i, 0.0f);
+    }
+    const int64_t p0 = t_ptr[node];
+    const int deg = (int)(t_ptr[node + 1] - p0);            // a degree-0 source stores zeros
+    // next entry's id and target fetched one iteration ahead
+    int64_t en = deg > 0 ? t_edge[p0] : 0, in = deg > 0 ? t_tgt[p0] : 0;
+    for (int t = 0; t < deg; ++t) {
+        const int64_t e = en, i_t = in;
+        if (t + 1 < deg) {
+            en = t_edge[p0 + t + 1];
+            in = t_tgt[p0 + t + 1];
+        }
+        const float a = wa[e * H + head], ds = wds[e * H + head];
+        const T qi = *(const T *)(q + i_t * HC + ch);
+        const T gi = *(const T *)(g + i_t * HC + ch);
+#pragma unroll
+        for (int i = 0; i < kVec; ++i) {
+            V::set(ak, i, V::get(ak, i) + ds * V::get(qi, i));
+            V::set(av, i, V::get(av, i) + a * V::get(gi, i));
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kVec; ++i) V::set(ak, i, V::get(ak, i) * scale);
+    *(T *)(dk + node * HC + ch) = ak;
+    *(T *)(dv + node * HC + ch) = av;
+}
+
+int64_t attn_backward_work_floats(int64_t n_edges, int heads, int HC) {
+    return 2 * n_edges * heads + (int64_t)kBwdMaxBlocks * HC;
+}
+
+hipError_t launch_attn_backward(const float *g, const float *q, const float *k, const float *v,
+                                const float *edge_w, const float *w_e, const int64_t *row_ptr,
+                                const int32_t *col, const float *out, const float *skip, const float *lse,
+                                const int64_t *t_ptr, const int32_t *t_edge, const int32_t *t_tgt,
+                                int64_t n_nodes, int64_t n_edges, int HC, int C, float scale, float *work,
+                                float *dq, float *dk, float *dv, float *dedge_w, float *dw_e, hipStream_t s) {
+    const bool vec4 =
+        C % 4 == 0 && HC % 4 == 0 &&
+        ((uintptr_t)g | (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dq |
+         (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)(skip ? skip : out) | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
+    const int vec = vec4 ? 4 : 1;
+    int lp = 1;
+    while (lp * vec < HC) lp <<= 1;
+    if (lp > kWave) return hipErrorInvalidValue;
+    const int npw = kWave / lp;
+    const int64_t waves = (n_nodes + npw - 1) / npw;
+    const int64_t groups = (waves + 3) / 4;
+    const unsigned blocks_a = (unsigned)(groups < kBwdMaxBlocks ? groups : kBwdMaxBlocks);
+    const unsigned blocks_b = (unsigned)groups;
+    const int H = HC / C;
+    float *wa = work, *wds = work + n_edges * H, *part = dw_e ? work + 2 * n_edges * H : nullptr;
+    (void)hipGetLastError();
+#define GSM_ATTN_BWD(LP, VEC)                                                                              \
+    do {                                                                                                   \
+        gsm_attn_bwd_target_kernel<LP, VEC><<<blocks_a, 256, 0, s>>>(g, q, k, v, edge_w, w_e, row_ptr, col, \
+                                                                     out, skip, lse, n_nodes, groups, HC, C, \
+                                                                     scale, wa, wds, part, dq, dedge_w);    \
+        gsm_attn_bwd_source_kernel<LP, VEC><<<blocks_b, 256, 0, s>>>(g, q, wa, wds, t_ptr, t_edge, t_tgt,   \
+                                                                     n_nodes, HC, C, scale, dk, dv);        \
+    } while (0)
+    if (vec4) {
+        switch (lp) {
+            case 1: GSM_ATTN_BWD(1, 4); break;
+            case 2: GSM_ATTN_BWD(2, 4); break;
+            case 4: GSM_ATTN_BWD(4, 4); break;
+            case 8: GSM_ATTN_BWD(8, 4); break;
+            case 16: GSM_ATTN_BWD(16, 4); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (lp) {
+            case 1: GSM_ATTN_BWD(1, 1); break;
+            case 2: GSM_ATTN_BWD(2, 1); break;
+            case 4: GSM_ATTN_BWD(4, 1); break;
+            case 8: GSM_ATTN_BWD(8, 1); break;
+            case 16: GSM_ATTN_BWD(16, 1); break;
+            case 32: GSM_ATTN_BWD(32, 1); break;
+            case 64: GSM_ATTN_BWD(64, 1); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
+#undef GSM_ATTN_BWD
+    if (dw_e) gsm_attn_bwd_dwe_kernel<<<1, 64 * kBwdSumRows, 0, s>>>(part, (int)blocks_a, HC, dw_e);
     return hipGetLastError();
 }
 

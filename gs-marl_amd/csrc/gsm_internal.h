@@ -258,7 +258,16 @@ hipError_t launch_emit_kernel(const DevParams &p, hipStream_t s);
 hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w,
                                  const float *w_e, const int64_t *row_ptr, const int32_t *col,
                                  const float *skip, int64_t n_nodes, int HC, int C, float scale, float *out,
-                                 hipStream_t s);
+                                 float *lse, hipStream_t s);
+// floats of workspace launch_attn_backward needs: a_ij and ds_ij per (entry,
+// head), then the dw_e block partials
+int64_t attn_backward_work_floats(int64_t n_edges, int heads, int HC);
+hipError_t launch_attn_backward(const float *g, const float *q, const float *k, const float *v,
+                                const float *edge_w, const float *w_e, const int64_t *row_ptr,
+                                const int32_t *col, const float *out, const float *skip, const float *lse,
+                                const int64_t *t_ptr, const int32_t *t_edge, const int32_t *t_tgt,
+                                int64_t n_nodes, int64_t n_edges, int HC, int C, float scale, float *work,
+                                float *dq, float *dk, float *dv, float *dedge_w, float *dw_e, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,
                          const int32_t *edge_index, int64_t edge_capacity, const int32_t *env_ids,
                          int32_t n_frames, float half_width, float r_agent, float r_target, float r_obst,

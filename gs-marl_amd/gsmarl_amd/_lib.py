@@ -97,6 +97,12 @@ SIGNATURES = {
                                       C.POINTER(C.c_float)]),
     "gsm_attn_aggregate": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float,
                                      _P, _P]),
+    "gsm_attn_aggregate_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_float, _P, _P, _P]),
+    "gsm_attn_backward_work_floats": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_int64)]),
+    "gsm_attn_aggregate_bwd": (C.c_int, [_P] * 14 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float] +
+                               [_P] * 7),
     "gsm_render": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gsm_debug_set_stamps": (C.c_int, [_P, _P]),

@@ -12,7 +12,11 @@ restates that layer:
   neighbours, weighted aggregation — is the HIP kernel behind
   ``gsm_attn_aggregate`` (gsm_gnn.hip) on the rollout / inference path, and the
   equivalent torch formulation (``attn_aggregate_ref``) where gradients are
-  needed (training) or as the numerics reference.
+  needed (training) or as the numerics reference;
+* ``attn_aggregate_autograd`` is the kernel with gradients (the HIP backward
+  ``gsm_attn_aggregate_bwd`` over the CSR rows and the transposed graph of
+  ``csr_transpose``; ``attn_aggregate_bwd_ref`` is its torch restatement), which
+  ``TransformerConv(kernel_backward=True)`` trains on.
 
 Graph format: CSR over targets (``row_ptr`` [n+1] int64, ``col`` int32
 sources, ``edge_w`` per CSR entry). The env graphs are symmetric (every radius
@@ -65,20 +69,177 @@ def attn_aggregate_ref(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, 
     return out
 
 
-def attn_aggregate(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, heads=1, scale=None):
-    """HIP kernel (no autograd): see gsm_attn_aggregate in include/gsm.h."""
+def attn_aggregate_bwd_ref(grad_out, q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, heads=1,
+                           scale=None):
+    """The gradients of ``attn_aggregate_ref`` written out (plain torch, fp32 or
+    fp64, any device): the restatement the backward kernels are written
+    against. With ``m_ij = v_j + e_ij`` and ``g_i = grad_out[i]``::
+
+        dskip_i    = g_i
+        D_i[h]     = sum_j a_ij <g_i[h], m_ij[h]>      (= <g_i[h], out_i[h] - skip_i[h]>)
+        ds_ij[h]   = a_ij[h] * (<g_i[h], m_ij[h]> - D_i[h])
+        dq_i[h]    = scale * sum_j ds_ij[h] * (k_j[h] + e_ij[h])
+        dk_j[h]    = scale * sum_{i: j in row i} ds_ij[h] * q_i[h]
+        dv_j[h]    =         sum_{i: j in row i} a_ij[h]  * g_i[h]
+        de_ij[c]   = scale * ds_ij[h(c)] * q_i[c] + a_ij[h(c)] * g_i[c]
+        dw_e[c]    = sum_ij edge_w_ij * de_ij[c]
+        dedge_w_ij = sum_c de_ij[c] * w_e[c]
+
+    Returns ``(dq, dk, dv, dedge_w, dw_e, dskip)``, None where the input is None."""
     n, HC = q.shape
     Cc = HC // heads
-    scale = 1.0 / math.sqrt(Cc) if scale is None else float(scale)
+    scale = 1.0 / math.sqrt(Cc) if scale is None else scale
+    deg = row_ptr[1:] - row_ptr[:-1]
+    tgt = torch.repeat_interleave(torch.arange(n, device=q.device), deg, output_size=col.numel())
+    src = col.to(torch.int64)
+    e = 0.0
+    if edge_w is not None:
+        e = edge_w[:, None] * w_e[None, :]
+    kj = (k[src] + e).view(-1, heads, Cc)
+    mj = (v[src] + e).view(-1, heads, Cc)
+    qi = q[tgt].view(-1, heads, Cc)
+    gi = grad_out[tgt].view(-1, heads, Cc)
+    s = (qi * kj).sum(-1) * scale                                              # [nE, H]
+    smax = torch.full((n, heads), -math.inf, device=q.device, dtype=q.dtype)
+    smax = smax.scatter_reduce(0, tgt[:, None].expand(-1, heads), s, reduce="amax", include_self=True)
+    a = torch.exp(s - smax[tgt])
+    den = torch.zeros(n, heads, device=q.device, dtype=q.dtype).index_add(0, tgt, a)
+    a = a / den[tgt]
+    gm = (gi * mj).sum(-1)
+    D = torch.zeros(n, heads, device=q.device, dtype=q.dtype).index_add(0, tgt, a * gm)
+    ds = a * (gm - D[tgt])
+    zero = torch.zeros(n, heads, Cc, device=q.device, dtype=q.dtype)
+    dq = (scale * zero.index_add(0, tgt, ds[..., None] * kj)).view(n, HC)
+    dk = (scale * zero.index_add(0, src, ds[..., None] * qi)).view(n, HC)
+    dv = zero.index_add(0, src, a[..., None] * gi).view(n, HC)
+    dedge_w = dw_e = None
+    if edge_w is not None:
+        de = (scale * ds[..., None] * qi + a[..., None] * gi).view(-1, HC)
+        dw_e = (edge_w[:, None] * de).sum(0)
+        dedge_w = (de * w_e[None, :]).sum(-1)
+    return dq, dk, dv, dedge_w, dw_e, (grad_out if skip is not None else None)
+
+
+def csr_transpose(row_ptr, col):
+    """The CSR entries regrouped by source, for the sums of the backward that
+    run over the rows containing a source: ``(t_ptr int64 [n+1], t_edge int32
+    [nE], t_tgt int32 [nE])``: offsets per source, the entry ids of each source
+    in ascending order (a stable sort) and each listed entry's target row. A
+    property of the graph alone: build it once per stored graph."""
+    n, nE = row_ptr.numel() - 1, col.numel()
+    dev = col.device
+    src = col.to(torch.int64)
+    perm = torch.sort(src, stable=True)[1]
+    t_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(src, minlength=n), 0, out=t_ptr[1:])
+    tgt = torch.repeat_interleave(torch.arange(n, device=dev), row_ptr[1:] - row_ptr[:-1], output_size=nE)
+    return t_ptr, perm.to(torch.int32), tgt[perm].to(torch.int32)
+
+
+def _check_kernel_inputs(q, k, v, row_ptr, col, edge_w, w_e, what):
     dev = q.device
     if dev.type != "cuda":
-        raise _lib.GsmError("attn_aggregate needs a ROCm GPU; use attn_aggregate_ref on the CPU")
+        raise _lib.GsmError(f"{what} needs a ROCm GPU; use attn_aggregate_ref on the CPU")
     for name, t, dt in (("q", q, torch.float32), ("k", k, torch.float32), ("v", v, torch.float32),
                         ("row_ptr", row_ptr, torch.int64), ("col", col, torch.int32)):
         if t.dtype != dt or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"{name}: need a contiguous {dt} tensor on {dev}")
     if edge_w is not None and (edge_w.dtype != torch.float32 or w_e is None):
         raise ValueError("edge_w: float32, with w_e")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class _AttnAggregateFn(torch.autograd.Function):
+    """gsm_attn_aggregate_fwd / gsm_attn_aggregate_bwd (include/gsm.h)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, row_ptr, col, edge_w, w_e, skip, heads, scale, t_ptr, t_edge, t_tgt):
+        n, HC = q.shape
+        lib = _lib.load()
+        out = torch.empty_like(q)
+        lse = torch.empty(n, heads, dtype=torch.float32, device=q.device)
+        # an empty tensor has no address; without edges the kernel reads neither col nor the edge terms
+        col_arg = col if col.numel() else col.new_zeros(1)
+        ew_arg, we_arg = (edge_w, w_e) if col.numel() else (None, None)
+        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        rc = lib.gsm_attn_aggregate_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(ew_arg), _ptr(we_arg), _ptr(row_ptr),
+                                        _ptr(col_arg), _ptr(skip), int(n), int(heads), int(HC // heads), scale,
+                                        _ptr(out), _ptr(lse), stream)
+        _lib.check(lib, rc, None, "gsm_attn_aggregate_fwd")
+        ctx.save_for_backward(q, k, v, row_ptr, col, edge_w, w_e, skip, out, lse, t_ptr, t_edge, t_tgt)
+        ctx.heads, ctx.scale = heads, scale
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, row_ptr, col, edge_w, w_e, skip, out, lse, t_ptr, t_edge, t_tgt = ctx.saved_tensors
+        n, HC = q.shape
+        nE, heads = col.numel(), ctx.heads
+        lib = _lib.load()
+        g = grad_out.to(torch.float32).contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+        dedge_w = torch.empty_like(edge_w) if (ctx.needs_input_grad[5] and edge_w is not None) else None
+        dw_e = torch.empty_like(w_e) if (ctx.needs_input_grad[6] and w_e is not None) else None
+        nf = C.c_int64()
+        _lib.check(lib, lib.gsm_attn_backward_work_floats(int(n), int(nE), int(heads), int(HC // heads),
+                                                          C.byref(nf)), None, "gsm_attn_backward_work_floats")
+        work = torch.empty(nf.value, dtype=torch.float32, device=q.device)
+        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        ew_arg, we_arg = (edge_w, w_e) if nE else (None, None)
+        rc = lib.gsm_attn_aggregate_bwd(_ptr(g), _ptr(q), _ptr(k), _ptr(v), _ptr(ew_arg), _ptr(we_arg), _ptr(row_ptr),
+                                        _ptr(col), _ptr(out), _ptr(skip), _ptr(lse), _ptr(t_ptr), _ptr(t_edge),
+                                        _ptr(t_tgt), int(n), int(nE), int(heads), int(HC // heads), ctx.scale,
+                                        _ptr(work), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dedge_w), _ptr(dw_e),
+                                        stream)
+        _lib.check(lib, rc, None, "gsm_attn_aggregate_bwd")
+        dskip = g if (ctx.needs_input_grad[7] and skip is not None) else None
+        return dq, dk, dv, None, None, dedge_w, dw_e, dskip, None, None, None, None, None
+
+
+def attn_aggregate_autograd(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, heads=1, scale=None,
+                            transpose=None):
+    """``attn_aggregate`` with gradients: forward and backward both on the HIP
+    kernels (gsm_attn_aggregate_fwd / gsm_attn_aggregate_bwd in include/gsm.h).
+    Gradients go to q, k, v, skip, w_e and edge_w; no double backward.
+    ``transpose`` is ``csr_transpose(row_ptr, col)``; it is built here when it
+    is not passed in, so pass it when the graph is reused."""
+    n, HC = q.shape
+    Cc = HC // heads
+    scale = 1.0 / math.sqrt(Cc) if scale is None else float(scale)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    _check_kernel_inputs(q, k, v, row_ptr, col, edge_w, w_e, "attn_aggregate_autograd")
+    if edge_w is not None:
+        edge_w, w_e = edge_w.contiguous(), w_e.contiguous()
+        if edge_w.numel() != col.numel() or w_e.numel() != HC:
+            raise ValueError("edge_w: one weight per CSR entry; w_e: heads*channels")
+    if skip is not None:
+        skip = skip.contiguous()
+    if k.shape != q.shape or v.shape != q.shape or row_ptr.numel() != n + 1 or (
+            skip is not None and skip.shape != q.shape):
+        raise ValueError("q, k, v, skip: [n, heads*channels]; row_ptr: [n+1]")
+    needs = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, edge_w, w_e, skip))
+    if needs and transpose is None:
+        transpose = csr_transpose(row_ptr, col)
+    t_ptr, t_edge, t_tgt = transpose if transpose is not None else (None, None, None)
+    if transpose is not None:
+        for name, t, dt, m in (("t_ptr", t_ptr, torch.int64, n + 1), ("t_edge", t_edge, torch.int32, col.numel()),
+                               ("t_tgt", t_tgt, torch.int32, col.numel())):
+            if t.dtype != dt or not t.is_contiguous() or t.device != q.device or t.numel() != m:
+                raise ValueError(f"{name}: need a contiguous {dt} tensor of {m} on {q.device}")
+    return _AttnAggregateFn.apply(q, k, v, row_ptr, col, edge_w, w_e, skip, int(heads), scale, t_ptr, t_edge, t_tgt)
+
+
+def attn_aggregate(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, heads=1, scale=None):
+    """HIP kernel (no autograd): see gsm_attn_aggregate in include/gsm.h."""
+    n, HC = q.shape
+    Cc = HC // heads
+    scale = 1.0 / math.sqrt(Cc) if scale is None else float(scale)
+    dev = q.device
+    _check_kernel_inputs(q, k, v, row_ptr, col, edge_w, w_e, "attn_aggregate")
     lib = _lib.load()
     out = torch.empty_like(q)
 
@@ -96,10 +257,15 @@ def attn_aggregate(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, head
 class TransformerConv(torch.nn.Module):
     """``TransformerConv(in_channels, out_channels, heads, concat, edge_dim=1,
     root_weight=True)`` in the torch-geometric parameterisation, with the
-    aggregation on the HIP kernel when no gradient is needed."""
+    aggregation on the HIP kernel when no gradient is needed. With
+    ``kernel_backward=True`` (and ``use_kernel``, on the GPU) the training path
+    takes the HIP forward and backward kernels (``attn_aggregate_autograd``)
+    too; ``forward(..., transpose=csr_transpose(row_ptr, col))`` reuses the
+    transposed graph across calls. The default keeps the torch formulation."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
-                 edge_dim: Optional[int] = 1, root_weight: bool = True, use_kernel: bool = True):
+                 edge_dim: Optional[int] = 1, root_weight: bool = True, use_kernel: bool = True,
+                 kernel_backward: bool = False):
         super().__init__()
         self.heads, self.out_channels, self.concat = heads, out_channels, concat
         HC = heads * out_channels
@@ -109,16 +275,21 @@ class TransformerConv(torch.nn.Module):
         self.lin_edge = torch.nn.Linear(edge_dim, HC, bias=False) if edge_dim else None
         self.lin_skip = torch.nn.Linear(in_channels, HC if concat else out_channels) if root_weight else None
         self.use_kernel = use_kernel
+        self.kernel_backward = kernel_backward
 
     def forward(self, x: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor,
-                edge_attr: Optional[torch.Tensor] = None) -> torch.Tensor:
+                edge_attr: Optional[torch.Tensor] = None, transpose=None) -> torch.Tensor:
         n = x.shape[0]
         q, k, v = self.lin_query(x), self.lin_key(x), self.lin_value(x)
         w_e = self.lin_edge.weight[:, 0] if (self.lin_edge is not None and edge_attr is not None) else None
         ew = edge_attr.reshape(-1) if w_e is not None else None
         skip = self.lin_skip(x) if (self.lin_skip is not None and self.concat) else None
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if self.use_kernel and x.is_cuda and not grad:
+        needs = torch.is_grad_enabled() and (grad or x.requires_grad or (ew is not None and ew.requires_grad))
+        if self.use_kernel and self.kernel_backward and x.is_cuda and needs:
+            out = attn_aggregate_autograd(q, k, v, row_ptr, col.to(torch.int32), ew, w_e, skip, self.heads,
+                                          transpose=transpose)
+        elif self.use_kernel and x.is_cuda and not grad:
             out = attn_aggregate(q.contiguous(), k.contiguous(), v.contiguous(), row_ptr, col.to(torch.int32),
                                  ew, w_e, skip, self.heads)
         else:

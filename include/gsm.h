@@ -351,6 +351,43 @@ int gsm_graph_kernel_ms(gsm_handle *h, int32_t slot, float *step_mean_ms, float 
 int gsm_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w, const float *w_e,
                        const int64_t *row_ptr, const int32_t *col, const float *skip, int64_t n_nodes,
                        int32_t heads, int32_t channels, float scale, float *out, void *stream);
+/* The same launch and the same `out`, and the row softmax statistics the
+ * backward needs: lse[i][h] = max_j s_ij + log(sum_j exp(s_ij - max)), device
+ * f32 [n_nodes][heads] (an empty row stores 0, which is never read). */
+int gsm_attn_aggregate_fwd(const float *q, const float *k, const float *v, const float *edge_w,
+                           const float *w_e, const int64_t *row_ptr, const int32_t *col, const float *skip,
+                           int64_t n_nodes, int32_t heads, int32_t channels, float scale, float *out, float *lse,
+                           void *stream);
+
+/* Gradients of gsm_attn_aggregate. With m_ij = v_j + e_ij, s_ij the scaled
+ * score and g_i = grad_out[i] (dskip = grad_out is left to the caller):
+ *   D_i[h]   = <g_i[h], out_i[h] - skip_i[h]>
+ *   ds_ij[h] = a_ij[h] * (<g_i[h], m_ij[h]> - D_i[h]),  a_ij = exp(s_ij - lse_i)
+ *   dq_i[h]  = scale * sum_j ds_ij[h] (k_j[h] + e_ij[h])
+ *   dk_j[h]  = scale * sum_{i: j in row i} ds_ij[h] q_i[h]
+ *   dv_j[h]  =         sum_{i: j in row i} a_ij[h]  g_i[h]
+ *   de_ij[c] = scale * ds_ij[h(c)] q_i[c] + a_ij[h(c)] g_i[c]
+ *   dw_e[c]  = sum_ij edge_w[ij] de_ij[c],   dedge_w[ij] = sum_c de_ij[c] w_e[c]
+ * out, lse: what gsm_attn_aggregate_fwd wrote for the same inputs. The sums
+ * over the rows that contain j run over the transposed graph: t_ptr int64
+ * [n_nodes+1] offsets per source, t_edge int32 [n_edges] the CSR entry ids
+ * grouped by source (ascending within a source), t_tgt int32 [n_edges] each
+ * listed entry's target row. work: device f32, gsm_attn_backward_work_floats
+ * of them (a_ij and ds_ij per entry and head, and the dw_e block partials).
+ * dq, dk, dv: f32 [n_nodes][heads*channels], every row written (a node that
+ * is nobody's source gets dk = dv = 0); dedge_w f32 [n_edges] and dw_e f32
+ * [heads*channels] may be NULL (not wanted). No atomics: the outputs are
+ * bitwise reproducible. Shape limits as the forward; n_edges < 2^31; with
+ * n_nodes == 0 or n_edges == 0 the gradients are zeros. Stateless;
+ * asynchronous on `stream`. */
+int gsm_attn_backward_work_floats(int64_t n_nodes, int64_t n_edges, int32_t heads, int32_t channels,
+                                  int64_t *n_floats);
+int gsm_attn_aggregate_bwd(const float *grad_out, const float *q, const float *k, const float *v,
+                           const float *edge_w, const float *w_e, const int64_t *row_ptr, const int32_t *col,
+                           const float *out, const float *skip, const float *lse, const int64_t *t_ptr,
+                           const int32_t *t_edge, const int32_t *t_tgt, int64_t n_nodes, int64_t n_edges,
+                           int32_t heads, int32_t channels, float scale, float *work, float *dq, float *dk,
+                           float *dv, float *dedge_w, float *dw_e, void *stream);
 
 /* Episode frames (replaces the pyglet viewer of
  * multiagent/rendering.py, SOURCES.txt:18, used by scripts/render_mpe.py,

@@ -1,0 +1,238 @@
+"""gsm_attn_aggregate_fwd / gsm_attn_aggregate_bwd (HIP, gsm_gnn.hip) behind
+gnn.attn_aggregate_autograd, against the written-out backward
+(gnn.attn_aggregate_bwd_ref) in fp64, on random CSR graphs with planted hard
+cases: a hub source, one long row, a self loop, a duplicated entry, a node
+that is never a source, empty rows, a ragged last wave (n = 1003).
+
+Tolerance: the forward's criterion, err <= 2e-5 * (1 + |ref|) against fp64,
+for dq, dk, dv and dedge_w. dw_e sums one term per edge and channel, so its
+bound scales with the sum of the terms' magnitudes: err <= 2e-5 * (1 +
+sum_ij |edge_w_ij de_ij[c]|). The fp32 torch formulation's autograd error
+against the same fp64 reference is measured alongside and printed."""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from gsmarl_amd import gnn
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+BOUND = 2e-5
+N = 1003
+HUB, LONG, LOOP, DUP, NEVER = 5, 17, 20, 30, 77
+SHAPES = [(1, 1), (3, 2), (1, 4), (2, 8), (3, 16), (4, 16), (1, 64)]
+OPTS = [(True, True), (False, False)]
+NAMES = ("dq", "dk", "dv", "dedge_w", "dw_e", "dskip")
+
+
+def _graph(n, rng, max_deg=6, empty=0.2):
+    """test_gpu_gnn._graph's recipe, with the hard cases planted."""
+    deg = rng.integers(0, max_deg + 1, size=n)
+    deg[rng.random(n) < empty] = 0
+    deg[LONG], deg[LOOP], deg[DUP], deg[NEVER] = 40, 3, 3, 2
+    ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(deg, out=ptr[1:])
+    col = rng.integers(0, n, size=int(ptr[-1])).astype(np.int32)
+    rows = np.flatnonzero(deg > 0)
+    rows = rows[~np.isin(rows, (LOOP, DUP))]
+    col[ptr[rng.choice(rows, size=300, replace=False)]] = HUB      # a hub source in 300 rows
+    col[col == NEVER] = NEVER + 1                                  # nobody's source
+    col[ptr[LOOP]] = LOOP                                          # a self loop
+    col[ptr[DUP] + 1] = col[ptr[DUP]]                              # a duplicated (i, j)
+    assert (deg == 0).sum() > 50 and deg[deg != 40].max() <= 6 and (col == HUB).sum() >= 300
+    return torch.from_numpy(ptr).to(DEV), torch.from_numpy(col).to(DEV)
+
+
+def _edge_term_sums(g, q, k, v, ptr, col, ew, we, heads):
+    """sum_ij |edge_w_ij de_ij[c]| in the inputs' precision (the scale of dw_e's bound)."""
+    n, HC = q.shape
+    Cc = HC // heads
+    scale = 1.0 / math.sqrt(Cc)
+    tgt = torch.repeat_interleave(torch.arange(n, device=q.device), ptr[1:] - ptr[:-1])
+    src = col.to(torch.int64)
+    e = ew[:, None] * we[None, :]
+    qi, gi = q[tgt].view(-1, heads, Cc), g[tgt].view(-1, heads, Cc)
+    s = (qi * (k[src] + e).view(-1, heads, Cc)).sum(-1) * scale
+    gm = (gi * (v[src] + e).view(-1, heads, Cc)).sum(-1)
+    smax = torch.full((n, heads), -math.inf, device=q.device, dtype=q.dtype)
+    smax = smax.scatter_reduce(0, tgt[:, None].expand(-1, heads), s, reduce="amax", include_self=True)
+    a = torch.exp(s - smax[tgt])
+    a = a / torch.zeros(n, heads, device=q.device, dtype=q.dtype).index_add(0, tgt, a)[tgt]
+    D = torch.zeros(n, heads, device=q.device, dtype=q.dtype).index_add(0, tgt, a * gm)
+    ds = a * (gm - D[tgt])
+    de = (scale * ds[..., None] * qi + a[..., None] * gi).view(-1, HC)
+    return (ew[:, None] * de).abs().sum(0)
+
+
+def _run_kernel(c, transpose, edge_grad=True):
+    ins = {n_: (c[n_].clone().requires_grad_(True) if c[n_] is not None else None)
+           for n_ in ("q", "k", "v", "ew", "we", "sk")}
+    if not edge_grad and ins["ew"] is not None:
+        ins["ew"].requires_grad_(False)
+    out = gnn.attn_aggregate_autograd(ins["q"], ins["k"], ins["v"], c["ptr"], c["col"], ins["ew"], ins["we"],
+                                      ins["sk"], c["heads"], transpose=transpose)
+    out.backward(c["g"])
+    grads = tuple(ins[n_].grad if ins[n_] is not None else None for n_ in ("q", "k", "v", "ew", "we", "sk"))
+    return out.detach(), grads
+
+
+@functools.lru_cache(maxsize=None)
+def _case(heads, C, edge, skip):
+    rng = np.random.default_rng(heads * 100 + C)
+    ptr, col = _graph(N, rng)
+    HC = heads * C
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    q, k, v, sk, g = (torch.randn(N, HC, device=DEV, generator=gen) for _ in range(5))
+    c = dict(heads=heads, ptr=ptr, col=col, q=q, k=k, v=v, g=g,
+             ew=torch.rand(col.numel(), device=DEV, generator=gen) if edge else None,
+             we=torch.randn(HC, device=DEV, generator=gen) if edge else None, sk=sk if skip else None)
+    d = {n_: (c[n_].double() if c[n_] is not None else None) for n_ in ("q", "k", "v", "g", "ew", "we", "sk")}
+    c["ref"] = gnn.attn_aggregate_bwd_ref(d["g"], d["q"], d["k"], d["v"], ptr, col, d["ew"], d["we"], d["sk"], heads)
+    c["dwe_scale"] = 1 + _edge_term_sums(d["g"], d["q"], d["k"], d["v"], ptr, col, d["ew"], d["we"], heads) \
+        if edge else None
+    # the fp32 torch formulation's autograd, for the error it makes against the same reference
+    ins = [t.clone().requires_grad_(True) if t is not None else None for t in (q, k, v, c["ew"], c["we"], c["sk"])]
+    out = gnn.attn_aggregate_ref(ins[0], ins[1], ins[2], ptr, col, ins[3], ins[4], ins[5], heads)
+    out.backward(g)
+    c["torch32"] = tuple(t.grad if t is not None else None for t in ins)
+    c["transpose"] = gnn.csr_transpose(ptr, col)
+    c["out"], c["grads"] = _run_kernel(c, c["transpose"])
+    return c
+
+
+def _norm_err(c, grads):
+    """max over elements of err / (1 + |ref|) (dw_e: / (1 + sum |terms|)), per output."""
+    res = {}
+    for name, got, ref in zip(NAMES, grads, c["ref"]):
+        if ref is None:
+            assert got is None, name
+            continue
+        assert got is not None and got.shape == ref.shape and got.dtype == torch.float32, name
+        err = (got.double() - ref).abs()
+        den = c["dwe_scale"] if name == "dw_e" else 1 + ref.abs()
+        res[name] = float((err / den).max())
+    return res
+
+
+@pytest.mark.parametrize("heads,C", SHAPES)
+@pytest.mark.parametrize("edge,skip", OPTS)
+def test_backward_matches_reference(heads, C, edge, skip):
+    c = _case(heads, C, edge, skip)
+    kern, torch32 = _norm_err(c, c["grads"]), _norm_err(c, c["torch32"])
+    print(f"H{heads} C{C} edge={edge} skip={skip} normalised max error vs fp64: kernel {kern} | torch fp32 {torch32}")
+    for name, e in kern.items():
+        assert e <= BOUND, (name, e, torch32[name])
+
+
+@pytest.mark.parametrize("heads,C", SHAPES)
+@pytest.mark.parametrize("edge,skip", OPTS)
+def test_exact_rows_and_forward(heads, C, edge, skip):
+    c = _case(heads, C, edge, skip)
+    dq, dk, dv, _, _, dsk = c["grads"]
+    if skip:
+        assert torch.equal(dsk, c["g"])                             # dskip is grad_out, bitwise
+    assert not bool((c["col"] == NEVER).any())
+    assert torch.count_nonzero(dk[NEVER]) == 0 and torch.count_nonzero(dv[NEVER]) == 0
+    empty = c["ptr"][1:] == c["ptr"][:-1]
+    assert int(empty.sum()) > 50 and torch.count_nonzero(dq[empty]) == 0
+    assert torch.count_nonzero(dk[HUB]) > 0 and torch.count_nonzero(dq[LONG]) > 0
+    # the forward is the inference kernel's, bit for bit
+    assert torch.equal(c["out"], gnn.attn_aggregate(c["q"], c["k"], c["v"], c["ptr"], c["col"], c["ew"], c["we"],
+                                                    c["sk"], heads))
+
+
+@pytest.mark.parametrize("heads,C", SHAPES)
+@pytest.mark.parametrize("edge,skip", OPTS)
+def test_backward_is_reproducible(heads, C, edge, skip):
+    c = _case(heads, C, edge, skip)
+    out, again = _run_kernel(c, None)                               # the transpose built inside this time
+    assert torch.equal(out, c["out"])
+    for name, a, b in zip(NAMES, again, c["grads"]):
+        assert (a is None and b is None) or torch.equal(a, b), name
+
+
+def test_edge_weight_without_grad():
+    c = _case(3, 16, True, True)
+    _, (dq, dk, dv, dew, dwe, dsk) = _run_kernel(c, c["transpose"], edge_grad=False)
+    assert dew is None
+    for a, b in zip((dq, dk, dv, dwe, dsk), [c["grads"][i] for i in (0, 1, 2, 4, 5)]):
+        assert torch.equal(a, b)
+    assert _norm_err(c, (dq, dk, dv, c["grads"][3], dwe, dsk))["dw_e"] <= BOUND
+
+
+def test_output_has_grad_fn_and_no_double_backward():
+    c = _case(2, 8, True, True)
+    q = c["q"].clone().requires_grad_(True)
+    out = gnn.attn_aggregate_autograd(q, c["k"], c["v"], c["ptr"], c["col"], c["ew"], c["we"], c["sk"], 2)
+    assert out.grad_fn is not None and "AttnAggregate" in type(out.grad_fn).__name__
+    with torch.no_grad():
+        assert gnn.attn_aggregate_autograd(q, c["k"], c["v"], c["ptr"], c["col"], heads=2).grad_fn is None
+    (dq,) = torch.autograd.grad(out, q, c["g"], create_graph=True)
+    with pytest.raises(RuntimeError):
+        dq.sum().backward()
+
+
+def test_no_edges_and_no_nodes():
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    col = torch.zeros(0, dtype=torch.int32, device=DEV)
+    for n in (5, 0):
+        ptr = torch.zeros(n + 1, dtype=torch.int64, device=DEV)
+        q, k, v, sk = (torch.randn(n, 8, device=DEV, generator=gen).requires_grad_(True) for _ in range(4))
+        ew = torch.zeros(0, device=DEV, requires_grad=True)
+        we = torch.randn(8, device=DEV, generator=gen).requires_grad_(True)
+        g = torch.randn(n, 8, device=DEV, generator=gen)
+        out = gnn.attn_aggregate_autograd(q, k, v, ptr, col, ew, we, sk, heads=2)
+        assert torch.equal(out, sk)
+        out.backward(g)
+        torch.cuda.synchronize()
+        for t in (q, k, v, we, ew):
+            assert t.grad is not None and t.grad.shape == t.shape and torch.count_nonzero(t.grad) == 0
+        assert torch.equal(sk.grad, g)
+
+
+def test_rejects_unsupported_shapes():
+    from gsmarl_amd._lib import GsmError
+    ptr = torch.zeros(5, dtype=torch.int64, device=DEV)
+    col = torch.zeros(0, dtype=torch.int32, device=DEV)
+    q = torch.zeros(4, 48, device=DEV, requires_grad=True)
+    with pytest.raises(GsmError):
+        gnn.attn_aggregate_autograd(q, q, q, ptr, col, heads=1)       # C = 48: not a power of two
+    q = torch.zeros(4, 128, device=DEV, requires_grad=True)
+    with pytest.raises(GsmError):
+        gnn.attn_aggregate_autograd(q, q, q, ptr, col, heads=2)       # H*C > 64
+
+
+def test_module_kernel_backward():
+    """TransformerConv(kernel_backward=True) against the same weights on the
+    torch formulation, on a small env graph: parameter and input gradients."""
+    from gsmarl_amd import EnvConfig, GpuBatchEnv
+    env = GpuBatchEnv(EnvConfig(n_agents=3, n_envs=64, seed=1), DEV)
+    o = env.reset(seed=1)
+    n = env.B * env.E
+    ptr = gnn.env_csr(o["edge_index"], n)
+    col = o["edge_index"][1].contiguous()
+    attr = o["edge_attr"].reshape(-1, 1).clone()
+    x0 = o["node_feat"].reshape(n, 7).clone()
+    torch.manual_seed(0)
+    conv_k = gnn.TransformerConv(7, 16, heads=3, kernel_backward=True).to(DEV)
+    conv_t = gnn.TransformerConv(7, 16, heads=3).to(DEV)
+    conv_t.load_state_dict(conv_k.state_dict())
+    w = torch.randn(n, 48, device=DEV)
+    tr = gnn.csr_transpose(ptr, col.to(torch.int32))
+    grads = []
+    for conv, kw in ((conv_k, dict(transpose=tr)), (conv_t, {})):
+        x = x0.clone().requires_grad_(True)
+        y = conv(x, ptr, col, attr, **kw)
+        is_fn = "AttnAggregate" in type(y.grad_fn).__name__
+        assert is_fn == conv.kernel_backward
+        (y * w).sum().backward()
+        grads.append([("x", x.grad)] + [(k_, p.grad) for k_, p in conv.named_parameters()])
+    for (name, a), (_, b) in zip(*grads):
+        assert a is not None and b is not None, name
+        err = (a - b).abs()
+        print(name, "max err", float(err.max()), "max normalised", float((err / (1 + b.abs())).max()))
+        assert torch.all(err <= BOUND * (1 + b.abs())), (name, float(err.max()))
+    env.close()
