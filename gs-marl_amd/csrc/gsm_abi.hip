@@ -1120,6 +1120,10 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     p.roll.csum_stride = kCsumStride;   // (csum, pace: set per launch, gsm_graph_launch)
     p.roll.gran_end = (uint64_t *)((char *)sl.gran + gran_alloc);
     p.roll.slab_end = h->slab ? (int32_t *)((char *)h->slab + h->slab_bytes) : nullptr;
+    // the segmented rollout's instantiation for the launch's arguments, final
+    // now (redirected outputs, pacing): the same LDS and no more registers
+    // than the generic one, so the occupancy found above holds
+    if (!tile && !ragged) roll_fn = gsm::roll_seg_kernel_fn(p, slots, sl.pace != nullptr);
     if (e == hipSuccess) {
         what = "rollout kernel node";
         hipKernelNodeParams kp = {};

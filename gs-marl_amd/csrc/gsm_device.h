@@ -110,6 +110,16 @@ __device__ __forceinline__ int wave_scan(int v) {
     return v;
 }
 
+// Region marks for the static per-region instruction census of a kernel
+// (tools/isa_regions.py, an assembly listing built with -DGSM_REGION_MARKS):
+// a comment line in the assembly where the source reaches the mark. Nothing
+// in any library build.
+#ifdef GSM_REGION_MARKS
+#define GSM_REGION(name) asm volatile("; gsm-region " name)
+#else
+#define GSM_REGION(name) do { } while (0)
+#endif
+
 // In-kernel phase stamps for diagnostic builds (-DGSM_STAMPS): lane 0 of each
 // wave records s_memtime at phase boundaries into p.stamps[wave][k]. Never
 // compiled into the product library.

@@ -206,7 +206,11 @@ const void *lag_step_seg_kernel_fn(const DevParams &p);
 const void *emit_seg_kernel_fn(const DevParams &p);
 // fused K-step rollout kernel (nullptr where the config has none: G > 1,
 // runtime shapes, other families) and its LDS bytes
-const void *roll_seg_kernel_fn(const DevParams &p, bool slots);   // slots: a rollout buffer's outputs
+// slots: a rollout buffer's outputs; paced (given with a launch's final
+// arguments): its launches carry pace counters, so the plain instantiation
+// may be chosen where the arguments hold the common configuration
+// (gsm_seg_kernels.hip roll_seg_plain)
+const void *roll_seg_kernel_fn(const DevParams &p, bool slots, bool paced = false);
 // the one-launch eager step (K = 1, device-side epoch; one env per wave shapes)
 const void *roll_seg_eager_kernel_fn(const DevParams &p);
 int roll_seg_envs_per_block(const DevParams &p);

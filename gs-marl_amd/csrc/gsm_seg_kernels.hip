@@ -550,15 +550,17 @@ __device__ __forceinline__ void emit_rows(const Shape<kN, kNo> &s, const Lane &L
 // prefix exchange (block_emit) and fills the wait at its barrier.
 // stage_rows returns the env's edge count, or -1 (nothing staged) when the
 // list exceeds the scratch.
+// `incl`: the inclusive wave scan of the lanes' list lengths (a lane's row
+// bits, plus 1 on agent lanes: the edge to its goal), formed here or, in the
+// fused rollout, kept from the step that formed the masks (row_scan_word).
 template <int kN, int kNo>
-__device__ __forceinline__ int stage_rows(const Lane &L, uint32_t *s_scr, int scr_cap, uint64_t mask) {
+__device__ __forceinline__ int stage_rows(const Lane &L, uint32_t *s_scr, int scr_cap, uint64_t mask, int incl) {
     constexpr int N = kN;
     static_assert(N <= 31 && kNo <= 32, "agent and obstacle column bits in one word each");
     const int m = L.m;
     const uint64_t mk = L.live ? mask : 0ull;
     const uint32_t lo = (uint32_t)mk & ((1u << N) - 1u), hi = (uint32_t)(mk >> N);
     const int c = __popc(lo) + __popc(hi) + (L.agent ? 1 : 0);
-    const int incl = wave_scan(c);
     const int a_total = __builtin_amdgcn_readlane(incl, N - 1);
     const int total = __builtin_amdgcn_readlane(incl, 63) + N;
     if (total > scr_cap) return -1;
@@ -572,6 +574,13 @@ __device__ __forceinline__ int stage_rows(const Lane &L, uint32_t *s_scr, int sc
     for (uint32_t w = hi; w; w &= w - 1) *at++ = src | ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
     wave_sync();
     return total;
+}
+template <int kN, int kNo>
+__device__ __forceinline__ int stage_rows(const Lane &L, uint32_t *s_scr, int scr_cap, uint64_t mask) {
+    const uint64_t mk = L.live ? mask : 0ull;
+    const uint32_t lo = (uint32_t)mk & ((1u << kN) - 1u), hi = (uint32_t)(mk >> kN);
+    const int c = __popc(lo) + __popc(hi) + (L.agent ? 1 : 0);
+    return stage_rows<kN, kNo>(L, s_scr, scr_cap, mask, wave_scan(c));
 }
 template <int kN, int kNo>
 __device__ __forceinline__ void write_staged(const Lane &L, const float2 *s_pos, const uint32_t *s_scr, int total,
@@ -1191,11 +1200,11 @@ __device__ __forceinline__ float2 roll_force(const Params &p, float4 a, bool age
 
 // LDS per wave of the segmented rollout: [positions E][positions E][positions
 // E] rounded to 16 B, [staging scratch 28 E] rounded to 16 B, [next forces N]
-// [row masks of 64 lanes]. Buffer j at j * 8 E: one multiply per use (a select
+// [row masks of 64 lanes][their list-length scan, a word per lane]. Buffer j at j * 8 E: one multiply per use (a select
 // between two bases cost four scalar instructions per use).
 constexpr int roll_lds_scr(int E) { return (24 * E + 15) & ~15; }
 constexpr int roll_lds_force(int E) { return roll_lds_scr(E) + ((28 * E + 15) & ~15); }
-constexpr int roll_lds_wave(int N, int E) { return roll_lds_force(E) + 8 * N + 8 * kWave; }
+constexpr int roll_lds_wave(int N, int E) { return roll_lds_force(E) + 8 * N + 8 * kWave + 4 * kWave; }
 
 // kSlots: per-step outputs at base + k * stride (a rollout buffer); else every
 // step into the bound buffers (the strides are 0 and fold away).
@@ -1207,7 +1216,15 @@ constexpr int roll_lds_wave(int N, int E) { return roll_lds_force(E) + 8 * N + 8
 // epoch's parity. No per-launch host state: a stream capture of env.step
 // (torch.cuda.graph around a policy and the step) records this launch and
 // every replay takes the next epoch.
-template <int kN, int kNo, int kFmt, bool kSlots, bool kEager = false>
+// kPlain: the launch's arguments hold the common configuration — no strict
+// mode, per-agent rewards, auto-reset, agent rows only (no redirected
+// outputs), no speed clamp, pacing on (roll_seg_plain, checked by the host at
+// selection) — so none of them is read or tested in the loop: their kernarg
+// loads, compares, branches and bodies are not compiled. Every other
+// operation and its order are the generic form's. (The degenerate flags stay
+// a run-time test, once in the last iteration: the Python package binds that
+// buffer in every config, so a variant without it would never be chosen.)
+template <int kN, int kNo, int kFmt, bool kSlots, bool kEager = false, bool kPlain = false>
 __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevParams p) {
     static_assert(kN > 0 && kN <= 31 && kNo <= 32 && kFmt >= 0, "compile-time shape, staged emission");
     static_assert(!(kSlots && kEager), "the eager step writes the bound or redirected outputs");
@@ -1233,7 +1250,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
     // still in the third; goals and obstacles (static within an episode) are
     // kept in all three. Compile-time layout (roll_kernel_lds): [positions] x 3,
     // [staging scratch], [the next step's agent forces], [the row masks of
-    // step k - 2].
+    // step k - 2], [the scan of their list lengths].
     constexpr int wstride = roll_lds_wave(N, E);
     unsigned char *wave_lds = smem + wave * wstride;
     float2 *const s_buf0 = (float2 *)wave_lds;
@@ -1242,6 +1259,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
     float *s_nf = (float *)(wave_lds + roll_lds_scr(E));
     float2 *s_force = (float2 *)(wave_lds + roll_lds_force(E));
     uint64_t *const s_row = (uint64_t *)(s_force + N);
+    uint32_t *const s_inc = (uint32_t *)(s_row + kWave);   // the scan kept beside the row masks
     // positions before step j, by j % 3
     auto pos_buf = [&](int j3) { return s_buf0 + j3 * E; };
     int *s_bc = (int *)(smem + kWavesPerBlock * wstride);   // [3][waves]: per-env edge counts by step % 3
@@ -1284,6 +1302,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
     // and the counters of the slot's next launch zeroed (none for one step)
     auto pacing = [] {
         if constexpr (kEager) return false;
+        else if constexpr (kPlain) return true;
         else return late_params().roll.pace != nullptr;
     };
     auto pace_ctr = [] { return (gu32 *)hand_chk(late_params().roll.pace + pace_key()); };
@@ -1361,16 +1380,19 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
     uint8_t deg = 0;                                        // App. A S16 flags of the final state
     // The edges of step t_first + j (j < K), emitted two iterations later
     // (iteration j + 2; the last two steps' by the tail after the loop): its
-    // positions kept in buffer pj3, its row masks `mask`, this workgroup's
+    // positions kept in buffer pj3, its row masks `mask` and the inclusive
+    // scan `inc` of their list lengths (formed at step time), this workgroup's
     // counts of it in s_bc[cj3]. `done`: the steps this workgroup has added to
     // its CU's pace counter (0: no pacing here, the tail).
-    auto emit_step = [&](const int j, const int pj3, const int cj3, const uint64_t mask, const int done,
-                         const Lane &L) {
+    auto emit_step = [&](const int j, const int pj3, const int cj3, const uint64_t mask, const int inc,
+                         const int done, const Lane &L) {
         const int *cb = s_bc + cj3 * kWavesPerBlock;   // this workgroup's counts of step j
         // the env's list staged first (needs only its own row counts)
+        GSM_REGION("staging");
         GSM_TNOW(te0);
-        const int staged = wave_live ? stage_rows<kN, kNo>(L, (uint32_t *)s_nf, scr_cap, mask) : -1;
+        const int staged = wave_live ? stage_rows<kN, kNo>(L, (uint32_t *)s_nf, scr_cap, mask, inc) : -1;
         GSM_ACC(p, L.b, 14, te0);   // diagnostic builds: staging (emission, below, adds to it)
+        GSM_REGION("prefix");
         GSM_TNOW(te1);
         // wave 0 forms the workgroup's offset (one hop: the chunk sums and its
         // chunk-mates' counts, published two iterations ago) and hands it to
@@ -1403,6 +1425,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         GSM_TNOW(te2);
         __syncthreads();
         GSM_ACC(p, L.b, 13, te2);   // waiting for it
+        GSM_REGION("write");
         GSM_TNOW(te3);
         if (done > 0) pace_set(__builtin_amdgcn_readfirstlane(s_red[1]));
         // (the prefix formed once by thread 0, not w < wave selects: those
@@ -1434,7 +1457,9 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         wave_sync();
         GSM_ACC(p, L.b, 14, te3);
     };
+    GSM_REGION("before the loop");
     int r3 = 0;                 // k % 3
+    int inc_oo = 0;             // the list-length scan of oo's rows (of the steps of this launch)
     bool relaid_prev = false;   // the previous iteration re-laid the env out (wave-uniform)
     for (int k = 0; k < K; ++k) {
         // lane-derived values re-formed every iteration (an asm barrier): held
@@ -1442,6 +1467,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         Lane L = L0;
         asm volatile("" : "+v"(L.lane), "+v"(L.m));
         const int m = L.m;
+        GSM_REGION("integration");
         GSM_TNOW(tw0);
         const uint32_t um = (uint32_t)m, ma = L.lane < N ? (uint32_t)L.lane : N - 1;
         // the next step's actions, in flight during this step
@@ -1466,11 +1492,11 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
                 Fx = Fc.x;
                 Fy = Fc.y;
             }
-            if (pc.strict && strict_bad(m, pi, N, M, [&](int c) { return s_cur[row_entity(c, N)]; })) {
+            if (!kPlain && pc.strict && strict_bad(m, pi, N, M, [&](int c) { return s_cur[row_entity(c, N)]; })) {
                 Fx = __builtin_nanf("");
                 Fy = __builtin_nanf("");
             }
-            const float dt = pc.dt, max_speed = pc.max_speed;
+            const float dt = pc.dt, max_speed = kPlain ? 0.0f : pc.max_speed;
             v.x = v.x * pc.omd;
             v.y = v.y * pc.omd;
             v.x = v.x + (Fx * pc.inv_mass) * dt;
@@ -1493,6 +1519,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         const bool done = L.live && t >= pc.EL;
 
         // observation pass on the post-physics positions
+        GSM_REGION("sweep");
         float2 pm = s_pos[row_entity(m, N)];
         uint64_t row, cand;
         int ccnt;
@@ -1505,6 +1532,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         if (k == 0) GSM_RSTAMP(p, L.b, 3);
 
         // reward / cost
+        GSM_REGION("reward and stores");
         float r = 0.0f;
         if (L.agent) {
             const float2 g = s_pos[N + m];
@@ -1513,22 +1541,32 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         }
         float rsum = wave_total(r);
         const int ci = L.agent ? ccnt : 0;
-        const int csum = wave_total(ci);
+        // The step's integer sums in one scan of a packed word: low half the
+        // lane's edge list length (its row bits, plus the edge to its goal on
+        // agent lanes), high half its collisions. Lane 63 holds both totals;
+        // the low half's inclusive scan is what the emission of this step
+        // stages its rows by two iterations on (stage_rows), kept with the
+        // row masks.
+        static_assert(M * M + 2 * N < (1 << 16) && (M - 1) * N < (1 << 15), "neither half of the scan word carries");
+        if (!L.live) row = 0;
+        int scan = wave_scan((__popcll(row) + (L.agent ? 1 : 0)) | (ci << 16));
+        int scan_tot = __builtin_amdgcn_readlane(scan, 63);
+        const int csum = scan_tot >> 16;
         if (L.agent) {
             // (32-bit byte offsets from the kernarg base: SGPR base + VGPR
             // offset stores, no 64-bit scalar address arithmetic per store)
             KernargParams &q = late_params();
             const uint32_t off = ((uint32_t)eb * (uint32_t)N + um) * 4u;
-            *(float *)((char *)(q.ro.rew + (kSlots ? k * q.ro.rc_s : 0)) + off) = q.shared_reward ? rsum : r;
+            *(float *)((char *)(q.ro.rew + (kSlots ? k * q.ro.rc_s : 0)) + off) = (!kPlain && q.shared_reward) ? rsum : r;
             *(float *)((char *)(q.ro.cost + (kSlots ? k * q.ro.rc_s : 0)) + off) = (float)ci;
         }
-        if (late_params().shared_reward) rsum *= (float)N;
+        if (!kPlain && late_params().shared_reward) rsum *= (float)N;
         if (L.live) {
             acc.x += rsum;
             acc.y += (float)csum;
         }
         bool reset = false;
-        if (done && late_params().auto_reset) {
+        if (done && (kPlain || late_params().auto_reset)) {
             reset = true;
             if (m == 0) late_params().ep_last[L.b] = acc;
         }
@@ -1558,10 +1596,13 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
                 coinc = coinc2;
                 Fn = Fn2;
             }
+            // (the new episode's rows: their list lengths scanned again)
+            if (!L.live) row = 0;
+            scan = wave_scan(__popcll(row) + (L.agent ? 1 : 0));
+            scan_tot = __builtin_amdgcn_readlane(scan, 63);
         }
         GSM_ACC(p, L.b, 15, tr0);   // diagnostic builds: the re-layout (and the test for it)
         const bool relaid = reset;
-        if (!L.live) row = 0;
         if constexpr (kFused) {
             if (L.agent) s_force[m] = Fn;
         }
@@ -1571,7 +1612,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         // velocities, masks, counters) stays on chip and is stored once, after
         // the loop
         KernargParams &q = late_params();
-        const bool any_statics = q.nf_full || __any(relaid);
+        const bool any_statics = (!kPlain && q.nf_full) || __any(relaid);
         if constexpr (kSlots) {
             // (a rollout buffer: every slot's rows in full; the nested form
             // measured 1.4% faster there, profiles/r5_ab/store_blocks)
@@ -1609,14 +1650,14 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
             const uint64_t nb = __ballot(L.agent && nonfinite2(pm));
             deg = (uint8_t)((coinc ? kDegCoincident : 0) | (nb ? kDegNonfinite : 0));
         }
-        const int edges = __popcll(row) + ((L.live && m == 0) ? 2 * N : 0);
-        const int wave_edges = wave_total(edges);
+        const int wave_edges = (scan_tot & 0xffff) + (wave_live ? N : 0);   // the goal rows: one edge each
         if (wave_live && L.lane == 0) {
             (q.ro.done + (kSlots ? k * q.ro.done_s : 0))[L.b] = done ? 1 : 0;
             if (kSlots || k == K - 1) (q.ro.ecount + (kSlots ? k * q.ro.ec_s : 0))[L.b] = wave_edges;
         }
 
         // publish the workgroup's edge sum of step t
+        GSM_REGION("publish");
         if (L.lane == 0) s_bc[r3 * kWavesPerBlock + wave] = wave_edges;
         GSM_ACC(p, L.b, 10, tw0);   // the step's work
         GSM_TNOW(tw1);
@@ -1657,7 +1698,8 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         if (k == K - 1) GSM_RSTAMP(p, L.b, 4);
         // the edges of step t - 2 (row masks kept in s_row, positions after
         // it in buffer (k + 2) % 3, its counts in s_bc[(k + 1) % 3])
-        if (k >= 2) emit_step(k - 2, r3n == 2 ? 0 : r3n + 1, r3n, s_row[L.lane], pacing() ? k : 0, L);
+        if (k >= 2) emit_step(k - 2, r3n == 2 ? 0 : r3n + 1, r3n, s_row[L.lane], (int)s_inc[L.lane], pacing() ? k : 0, L);
+        GSM_REGION("loop end");
         // this workgroup's step into its CU's pace counter (read back in the
         // next iteration's emission)
         if (threadIdx.x == 0 && pacing())
@@ -1666,7 +1708,9 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         // keep step t - 1's row masks for the next iteration's emission and
         // step t's for its sweep
         s_row[L.lane] = oo;
+        s_inc[L.lane] = (uint32_t)inc_oo;
         oo = row;
+        inc_oo = scan & 0xffff;
         cand_prev = L.agent ? cand : 0ull;
         // A re-layout (iteration k) puts the new episode's statics into
         // buffer (k + 1) % 3; the other two still hold the old ones, which the
@@ -1686,6 +1730,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         r3 = r3n;
         wave_sync();
     }
+    GSM_REGION("after the loop");
     // the final state (what the next launch or an eager step reads), stored
     // before the tail: its emissions wait for the last steps' offsets, and
     // these stores need none
@@ -1724,11 +1769,11 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
         // otherwise write step K - 2's edges at step K - 1's offset)
         if (K >= 2) {
             __syncthreads();
-            emit_step(K - 2, rm1, rm1 == 0 ? 2 : rm1 - 1, s_row[L.lane], 0, L);
+            emit_step(K - 2, rm1, rm1 == 0 ? 2 : rm1 - 1, s_row[L.lane], (int)s_inc[L.lane], 0, L);
         }
         GSM_RSTAMP(p, L.b, 6);
         __syncthreads();
-        emit_step(K - 1, r3, rm1, oo, 0, L);
+        emit_step(K - 1, r3, rm1, oo, inc_oo, 0, L);
         GSM_RSTAMP(p, L.b, 7);
     }
     GSM_RSTAMP(p, L0.b, 8);
@@ -2698,8 +2743,22 @@ bool roll_pack_split(const DevParams &p) {
 }
 int roll_block_threads(const DevParams &p) { return roll_pack_split(p) ? kPack2Block : block_threads(p); }
 
+// Whether a launch's arguments hold the common configuration that the
+// rollout's plain instantiation is compiled for (gsm_roll_seg_kernel kPlain);
+// `paced`: its launches carry pace counters (DevParams::Roll::pace, set per
+// launch). GSM_ROLL_PLAIN=0 keeps the generic instantiation everywhere (an
+// A/B knob: the outputs are the same either way).
+static bool roll_seg_plain(const DevParams &p, bool paced) {
+    static const bool on = [] {
+        const char *e = getenv("GSM_ROLL_PLAIN");
+        return !(e && *e && atoi(e) == 0);
+    }();
+    return on && paced && p.strict == 0 && p.shared_reward == 0 && p.auto_reset == 1 && p.nf_full == 0 &&
+           !(p.max_speed > 0.0f);
+}
+
 template <bool kSlots, bool kEager = false>
-static const void *pick_roll_seg(const DevParams &p) {
+static const void *pick_roll_seg(const DevParams &p, bool paced = false) {
     if constexpr (kEager) {   // (one env per wave only: the packed rollout keeps host epochs)
         if (roll_packed(p)) return nullptr;
     } else {
@@ -2726,13 +2785,29 @@ static const void *pick_roll_seg(const DevParams &p) {
             default: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 2, kSlots, kEager>); \
         }                                                                                        \
     }
+    // (the plain instantiation for the rollout into the bound buffers only:
+    // the rollout-buffer and eager forms keep the generic one)
+    if constexpr (!kSlots && !kEager) {
+        if (roll_seg_plain(p, paced)) {
+#define GSM_PICK_PLAIN(n, no)                                                                                  \
+    if (p.N == n && p.No == no) {                                                                              \
+        switch (p.action_fmt) {                                                                                \
+            case 0: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 0, false, false, true>);  \
+            case 1: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 1, false, false, true>);  \
+            default: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 2, false, false, true>); \
+        }                                                                                                      \
+    }
+            GSM_ROLL_SHAPES(GSM_PICK_PLAIN)
+#undef GSM_PICK_PLAIN
+        }
+    }
     GSM_ROLL_SHAPES(GSM_PICK)
 #undef GSM_PICK
     return nullptr;
 }
-const void *roll_seg_kernel_fn(const DevParams &p, bool slots) {
+const void *roll_seg_kernel_fn(const DevParams &p, bool slots, bool paced) {
     if (p.path != kPathSeg) return nullptr;
-    return slots ? pick_roll_seg<true>(p) : pick_roll_seg<false>(p);
+    return slots ? pick_roll_seg<true>(p, paced) : pick_roll_seg<false>(p, paced);
 }
 const void *roll_seg_eager_kernel_fn(const DevParams &p) {
     if (p.path != kPathSeg) return nullptr;
