@@ -902,8 +902,21 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     p.reseed = 0;
     const bool tile = p.path == gsm::kPathTile, ragged = p.path == gsm::kPathRagged;
     const bool slots = per_step != nullptr;
+    // pacing: the rank offset in quarter steps (GSM_ROLL_PACE, default 2;
+    // 0 = no pacing: an A/B knob, outputs are the same either way)
+    int pace_q = 0;
+    bool pace_on = true;
+    if (const char *ev = getenv("GSM_ROLL_PACE")) {
+        if (!strcmp(ev, "off"))
+            pace_on = false;
+        else
+            pace_q = std::max(0, atoi(ev));
+    }
+    // two envs per wave (gsm_roll_pair_kernel): its grid and LDS differ, so it
+    // is decided here (none of the arguments it depends on changes below)
+    const bool pair = !tile && !ragged && gsm::roll_seg_pair(p, slots, pace_on);
     const void *roll_fn = tile ? gsm::roll_tile_kernel_fn(p, slots)
-                               : ragged ? gsm::roll_ragged_kernel_fn(p, slots) : gsm::roll_seg_kernel_fn(p, slots);
+                               : ragged ? gsm::roll_ragged_kernel_fn(p, slots) : gsm::roll_seg_kernel_fn(p, slots, pair);
     if (!roll_fn && fallback) return kRollIneligible;
     if (!roll_fn) return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: no fused rollout kernel for this config "
                                              "(segmented path with a compiled shape, tile path with the "
@@ -936,12 +949,12 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
         if (per_step[0].edge_index) ro.cap = per_step[0].edge_capacity;
         // p now describes the last slot: the final emit launch writes it
     }
-    // segmented / ragged rollout: one env per wave whatever the config's G (4 per workgroup), or four
-    // small envs per wave (16 per workgroup)
-    const int per_blk = tile ? 1 : ragged ? gsm::kWavesPerBlock : gsm::roll_seg_envs_per_block(p);
+    // segmented / ragged rollout: one env per wave whatever the config's G (4 per workgroup), two
+    // per wave (8, gsm_roll_pair_kernel), or four small envs per wave (16 per workgroup)
+    const int per_blk = tile ? 1 : ragged ? gsm::kWavesPerBlock : gsm::roll_seg_envs_per_block(p, pair);
     const int nb = tile ? gsm::step_grid_blocks(p) : (p.B + per_blk - 1) / per_blk;
     const size_t roll_lds = tile ? gsm::roll_tile_kernel_lds(p)
-                                 : ragged ? gsm::roll_ragged_kernel_lds(p) : gsm::roll_kernel_lds(p);
+                                 : ragged ? gsm::roll_ragged_kernel_lds(p) : gsm::roll_kernel_lds(p, pair);
     // every workgroup resident at once (one residency round; a workgroup only
     // waits on lower-numbered ones, so this is for speed, not for progress)
     int dev = 0, per_cu = 0, n_cu = 0;
@@ -1061,16 +1074,6 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     e = gsm::launch_granule_init(sl.gran, gran_alloc, 0u, h->cap_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->cap_stream);
     if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "rollout granule init"); }
-    // pacing: the rank offset in quarter steps (GSM_ROLL_PACE, default 2;
-    // 0 = no pacing: an A/B knob, outputs are the same either way)
-    int pace_q = 0;
-    bool pace_on = true;
-    if (const char *ev = getenv("GSM_ROLL_PACE")) {
-        if (!strcmp(ev, "off"))
-            pace_on = false;
-        else
-            pace_q = std::max(0, atoi(ev));
-    }
     if (one_hop) {
         uint64_t *const after = sl.gran + 2 + (size_t)K * nb;
         sl.csum = after;
@@ -1123,7 +1126,13 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     // the segmented rollout's instantiation for the launch's arguments, final
     // now (redirected outputs, pacing): the same LDS and no more registers
     // than the generic one, so the occupancy found above holds
-    if (!tile && !ragged) roll_fn = gsm::roll_seg_kernel_fn(p, slots, sl.pace != nullptr);
+    if (!tile && !ragged) {
+        if (gsm::roll_seg_pair(p, slots, sl.pace != nullptr) != pair) {
+            drop_slot(sl);
+            return fail(h, GSM_ESTATE, "GSM_GRAPH_ROLL: the rollout kernel's form changed during the capture");
+        }
+        roll_fn = gsm::roll_seg_kernel_fn(p, slots, sl.pace != nullptr);
+    }
     if (e == hipSuccess) {
         what = "rollout kernel node";
         hipKernelNodeParams kp = {};

@@ -213,11 +213,15 @@ const void *emit_seg_kernel_fn(const DevParams &p);
 const void *roll_seg_kernel_fn(const DevParams &p, bool slots, bool paced = false);
 // the one-launch eager step (K = 1, device-side epoch; one env per wave shapes)
 const void *roll_seg_eager_kernel_fn(const DevParams &p);
-int roll_seg_envs_per_block(const DevParams &p);
+// whether a launch with these arguments runs the two-envs-per-wave rollout
+// (gsm_roll_pair_kernel: 8 envs per workgroup, its own LDS layout); decided
+// with the launch's final arguments, like the plain instantiation
+bool roll_seg_pair(const DevParams &p, bool slots, bool paced);
+int roll_seg_envs_per_block(const DevParams &p, bool pair = false);
 // the segmented rollout packs four small envs per wave (gsm_roll_pack_kernel):
 // per-wave CSR hand-off granules, as the ragged rollout (Roll::xW / xNG)
 bool roll_packed(const DevParams &p);   // 4 (one env per wave) or 16 (small envs, four per wave)
-size_t roll_kernel_lds(const DevParams &p);
+size_t roll_kernel_lds(const DevParams &p, bool pair = false);
 const void *roll_tile_kernel_fn(const DevParams &p, bool slots);   // nullptr unless p.tile_sym
 size_t roll_tile_kernel_lds(const DevParams &p);
 const void *step_ragged_kernel_fn();

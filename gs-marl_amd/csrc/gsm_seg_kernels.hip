@@ -1780,6 +1780,639 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
 }
 
 // ---------------------------------------------------------------------------
+// Fused rollout, TWO envs per wave (32 < M <= 64 with N, No <= 32; the
+// headline 24 + 24 shape). The one-env rollout above pays most of
+// a step per wave whatever the wave holds — reductions, stores, the hand-off,
+// exec scaffolding, most of it on the CU's shared scalar issue path (DESIGN.md
+// §5) — and uses 48 of 64 lanes. Here a wave holds envs 2w and 2w + 1 in its
+// two 32-lane halves. Lanes hold AGENT rows only (lane li = lane & 31 < N:
+// agent li of its half's env); obstacles are columns:
+//   * agent column j: d2, two compares, and the lane's own rad' / near bits
+//     accumulated with one v_addc each (the agent-agent block is symmetric and
+//     (-dx)^2 = dx^2 exactly: the bits of the transposed form above);
+//   * obstacle column o: the same, and the rad' compare's lane mask is
+//     obstacle row o's agent bits — low word env A, high word env B — put
+//     into lanes o and 32 + o of one register by two v_writelanes. The
+//     obstacle positions are staged once per episode as column pairs.
+// So lane li also carries OBSTACLE row li of its env: its agent bits from the
+// sweep, its obstacle-obstacle bits cached (recomputed at a re-layout), and
+// stages / stores that row after its agent row. Per-env values (t, episode,
+// acc, done, the reset decision) are per half; sums and scans are 32-lane DPP
+// forms. The float reward sum keeps the association of wave_total: the same
+// DPP sequence without its last step, read at lanes 31 and 63 (lanes >= N add
+// zeros there as here). A workgroup holds 8 envs; the hand-off (prefix_publish
+// / roll_prefix / pace_*) is the one-env kernel's with 8 counts per step.
+// Compiled for the plain configuration only (gsm_roll_seg_kernel kPlain, bound
+// outputs): every output is bit-identical to that kernel's.
+#define GSM_PAIR_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
+constexpr int kPairHalf = 32, kPairEnvs = 2 * kWavesPerBlock;   // lanes per env, envs per workgroup
+// LDS per env: [positions E] x 3, [staging scratch 28 E] (roll_lds_*), [next
+// forces N], [obstacle column pairs No]; per wave: two of those, then the row
+// masks of step k - 2 (agent rows, obstacle rows) and their scan, per lane
+constexpr int pair_lds_env(int N, int No, int E) { return roll_lds_force(E) + 8 * N + 8 * No; }
+constexpr int pair_lds_wave(int N, int No, int E) { return 2 * pair_lds_env(N, No, E) + (8 + 8 + 4) * kWave; }
+constexpr int pair_lds_block(int N, int No, int E) {
+    return kWavesPerBlock * pair_lds_wave(N, No, E) + 4 * (6 * kPairEnvs + 4);
+}
+
+// sums and scans within the 32-lane halves (rows 0-1 and 2-3)
+__device__ __forceinline__ int half_scan(int v) {   // inclusive
+    v += dpp_i<0x111>(v);
+    v += dpp_i<0x112>(v);
+    v += dpp_i<0x114>(v);
+    v += dpp_i<0x118>(v);
+    v += dpp_i<0x142, 0xa>(v);
+    return v;
+}
+__device__ __forceinline__ int half_sum_last(int v) {   // lanes 31 and 63 hold their half's sum
+    v += dpp_i<0xB1>(v);
+    v += dpp_i<0x4E>(v);
+    v += dpp_i<0x141>(v);
+    v += dpp_i<0x140>(v);
+    v += dpp_i<0x142, 0xa>(v);
+    return v;
+}
+__device__ __forceinline__ float half_sum_last(float v) {   // (wave_total's steps but the last)
+    v += dpp_f<0xB1>(v);
+    v += dpp_f<0x4E>(v);
+    v += dpp_f<0x141>(v);
+    v += dpp_f<0x140>(v);
+    v += dpp_f<0x142, 0xa>(v);
+    return v;
+}
+// the value of its half's last lane, on every lane
+__device__ __forceinline__ int half_last(int v, int h) {
+    const int a = __builtin_amdgcn_readlane(v, 31), b = __builtin_amdgcn_readlane(v, 63);
+    return h ? b : a;
+}
+
+template <int kN, int kNo, int kFmt>
+__global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(DevParams p) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    constexpr int N = kN, No = kNo, M = kN + kNo, E = 2 * kN + kNo;
+    static_assert(M > 32 && M <= 64 && N <= 31 && No <= 32 && N % 2 == 0 && No % 2 == 0 && kFmt >= 0,
+                  "two envs per wave: agent and obstacle rows in 32 lanes, column pairs");
+    static_assert(E <= 3 * kPairHalf, "an env's positions in three passes of its half");
+    static_assert(N * (M + 1) < (1 << 16) && No * M < (1 << 16), "neither half of the scan word carries");
+    constexpr uint32_t abits = (1u << N) - 1u;
+    constexpr int kEnvLds = pair_lds_env(N, No, E), wstride = pair_lds_wave(N, No, E);
+    constexpr int scr_cap = 7 * E;   // words of staging scratch per env
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & (kPairHalf - 1);
+    const int wb = (blockIdx.x * kWavesPerBlock + wave) * 2;   // the wave's first env
+    const int b = wb + h;                                       // this lane's env
+    const bool env_live = b < p.B;
+    const bool agent = env_live && li < N, obrow = env_live && li < No;
+    const int64_t eb = env_live ? b : p.B - 1;                  // (clamped: loads at valid addresses)
+    const uint32_t ma = li < N ? (uint32_t)li : N - 1, mo = li < No ? (uint32_t)li : No - 1;
+    unsigned char *const wave_lds = smem + wave * wstride;
+    unsigned char *const envl = wave_lds + h * kEnvLds;         // this lane's env
+    float2 *const s_buf0 = (float2 *)envl;
+    auto pos_buf = [&](int j3) { return s_buf0 + j3 * E; };     // positions before step j, by j % 3
+    float *const s_scr = (float *)(envl + roll_lds_scr(E));    // agent column pairs (sweep) / staging
+    float2 *const s_force = (float2 *)(envl + roll_lds_force(E));
+    float *const s_oxy = (float *)(s_force + N);                // obstacle column pairs [x x y y]
+    uint64_t *const s_rowa = (uint64_t *)(wave_lds + 2 * kEnvLds);
+    uint64_t *const s_rowo = s_rowa + kWave;
+    uint32_t *const s_inc = (uint32_t *)(s_rowo + kWave);
+    int *const s_bc = (int *)(smem + kWavesPerBlock * wstride);   // [3][envs]: edge counts by step % 3
+    int *const s_red = s_bc + 3 * kPairEnvs;                      // the workgroup's offset, pace level, rank, pad
+    int *const s_pre = s_red + 4;                                 // [3][envs]: exclusive prefix of the counts
+    const int slot = wave * 2 + h;                                // this lane's env within the workgroup
+
+    start_prio<3>();
+    const uint32_t epoch = p.roll.epoch;
+    auto pace_ctr = [] { return (gu32 *)hand_chk(late_params().roll.pace + pace_key()); };
+    uint32_t pace_v = 0;
+    const int nc = ((int)gridDim.x + kPrefixChunk - 1) / kPrefixChunk;
+    {   // the slot's next launch: chunk sums and pace counters zeroed; this workgroup's arrival
+        KernargParams &qz = late_params();
+        const int cs = qz.roll.csum_stride, n = qz.roll.K * nc;
+        uint64_t *const cz = qz.roll.csum_next;
+        for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
+            __hip_atomic_store((gu64 *)hand_chk(cz + (int64_t)i * cs), 0ull, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = blockIdx.x * kBlock + threadIdx.x; i < kPaceKeys; i += gridDim.x * kBlock)
+            __hip_atomic_store((gu32 *)hand_chk(qz.roll.pace_next + i * kPaceStride), 0u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0)
+            pace_v = __hip_atomic_fetch_add(pace_ctr(), kPaceArrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+
+    // ---- the state before step t_first and its actions (loads unconditional
+    // at clamped addresses, predicates on the values: seg_load)
+    const int K = p.roll.K, n_act = p.roll.n_actions;
+    int arow = p.roll.t_first % n_act;
+    const float2 *const pos_g = p.pos + eb * E;
+    const float2 x0 = pos_g[li], x1 = pos_g[li + kPairHalf];
+    const float2 x2 = pos_g[li + 2 * kPairHalf < E ? li + 2 * kPairHalf : E - 1];
+    int t = p.step_count[eb], ep = p.episode[eb];
+    float2 acc = p.ep_acc[eb];
+    float2 v = p.vel[eb * N + ma];
+    uint64_t cand_prev = p.contact_mask[eb * N + ma];
+    uint64_t oo_a = p.row_mask[eb * M + ma], oo_o = p.row_mask[eb * M + N + mo];   // the rows of the state
+    const float4 a0 = roll_action_load<kN, kFmt>(p, arow, eb, ma);
+    if (!agent) {
+        v = make_float2(0.0f, 0.0f);
+        cand_prev = 0ull;
+        oo_a = 0ull;
+    }
+    if (!obrow) oo_o = 0ull;
+    if (!env_live) {
+        t = ep = 0;
+        acc = make_float2(0.0f, 0.0f);
+    }
+    if (env_live) {
+        s_buf0[li] = s_buf0[E + li] = s_buf0[2 * E + li] = x0;
+        s_buf0[li + kPairHalf] = s_buf0[E + li + kPairHalf] = s_buf0[2 * E + li + kPairHalf] = x1;
+        if (li + 2 * kPairHalf < E)
+            s_buf0[li + 2 * kPairHalf] = s_buf0[E + li + 2 * kPairHalf] = s_buf0[2 * E + li + 2 * kPairHalf] = x2;
+    }
+    if (threadIdx.x == 0) s_red[2] = (int)(pace_v >> 24);   // the rank on the CU
+    wave_sync();
+    start_prio<2>();
+    // the obstacle columns of the env's current layout, as pairs [x_o x_o+1 y_o y_o+1]
+    auto stage_obstacles = [&](const float2 *sp) {
+        if (li < No) {
+            const float2 q = sp[2 * N + li];
+            const int at = (li >> 1) * 4 + (li & 1);
+            s_oxy[at] = q.x;
+            s_oxy[at + 2] = q.y;
+        }
+    };
+    stage_obstacles(s_buf0);
+    // the first step's force: its action, then the stored candidates in
+    // ascending collider order (gsm_roll_seg_kernel add_contacts)
+    if (agent) {
+        KernargParams &pc = late_params();
+        float2 F = roll_force<kFmt>(pc, a0, true);
+        const float2 pi = s_buf0[li];
+        const float dmin_aa = pc.dmin_aa, dmin_ao = pc.dmin_ao;
+        for (uint64_t cm = cand_prev; cm; cm &= cm - 1) {
+            const int c = __builtin_ctzll(cm);
+            const float2 pj = s_buf0[row_entity(c, N)];
+            const float dx = pi.x - pj.x, dy = pi.y - pj.y;
+            const float d2 = dx * dx + dy * dy;
+            const float f = contact_scale(pc, d2, c < N ? dmin_aa : dmin_ao);
+            F.x += f * dx;
+            F.y += f * dy;
+        }
+        s_force[li] = F;
+    }
+
+    // The sweep of both envs over all M columns from the positions at `sp`
+    // (this lane's env). rowa / cand / ccnt / Fn: agent row li as
+    // obs_sweep_g1 kForce forms them (same predicates, the same walk operation
+    // for operation); rowo: obstacle row li; coinc: the lane's env holds a
+    // coincident pair. full: the obstacle-obstacle bits recomputed, else those
+    // of oo_in.
+    auto sweep = [&](const float2 *sp, float2 pm, bool full, uint64_t oo_in, float4 anext, uint64_t &rowa,
+                     uint64_t &rowo, uint64_t &cand, int &ccnt, bool &coinc, float2 &Fn) {
+        KernargParams &q = late_params();
+        if (agent) {
+            const int at = (li >> 1) * 4 + (li & 1);
+            s_scr[at] = pm.x;
+            s_scr[at + 2] = pm.y;
+        }
+        // (lanes without an agent row: d2 ~ 1e36, every predicate false)
+        const float2 pcol = agent ? pm : make_float2(1.0e18f, 1.0e18f);
+        const float R2 = q.R2, cut2_aa = q.cut2_aa, cut2_ao = q.cut2_ao;
+        uint32_t ra = 0, na = 0, ro = 0, no = 0;   // reversed: bit (count - 1 - j) = column j
+        uint32_t oa = 0;                           // obstacle row li's agent bits
+        wave_sync();
+        const f32x2 px = {pcol.x, pcol.x}, py = {pcol.y, pcol.y};
+        auto pair_d2 = [&](float4 Q) {
+            const f32x2 dx = px - (f32x2){Q.x, Q.y};
+            const f32x2 dy = py - (f32x2){Q.z, Q.w};
+            return dx * dx + dy * dy;
+        };
+        const float4 *const xy4 = (const float4 *)s_scr, *const oxy4 = (const float4 *)s_oxy;
+#pragma unroll
+        for (int g = 0; g < N / 2; ++g) {
+            const f32x2 d2 = pair_d2(xy4[g]);
+            ra = shl1_add_lane(ra, __ballot(d2.x <= R2));
+            na = shl1_add_lane(na, __ballot(d2.x < cut2_aa));
+            ra = shl1_add_lane(ra, __ballot(d2.y <= R2));
+            na = shl1_add_lane(na, __ballot(d2.y < cut2_aa));
+        }
+        auto obstacle_column = [&](int o, float d2) {
+            const uint64_t b_rad = __ballot(d2 <= R2);
+            ro = shl1_add_lane(ro, b_rad);
+            no = shl1_add_lane(no, __ballot(d2 < cut2_ao));
+            oa = writelane_u32((uint32_t)b_rad, (uint32_t)o, oa);
+            oa = writelane_u32((uint32_t)(b_rad >> 32), (uint32_t)(kPairHalf + o), oa);
+        };
+#pragma unroll
+        for (int g = 0; g < No / 2; ++g) {
+            const f32x2 d2 = pair_d2(oxy4[g]);
+            obstacle_column(2 * g, d2.x);
+            obstacle_column(2 * g + 1, d2.y);
+        }
+        ra = __builtin_bitreverse32(ra) >> (32 - N);
+        na = __builtin_bitreverse32(na) >> (32 - N);
+        ro = __builtin_bitreverse32(ro) >> (32 - No);
+        no = __builtin_bitreverse32(no) >> (32 - No);
+        uint64_t r = ((uint64_t)ro << N) | ra;
+        const uint64_t near = ((uint64_t)no << N) | na;
+        if (agent) r &= ~(1ull << li);   // self
+        else r = 0ull;
+        uint64_t orow = (full ? 0ull : (oo_in & ~(uint64_t)abits)) | oa;
+        if (full && obrow) {
+            const float2 po = sp[2 * N + li];
+#pragma unroll 2
+            for (int k = 0; k < No; ++k) {
+                const float2 qk = sp[2 * N + k];
+                const float dx = po.x - qk.x, dy = po.y - qk.y;
+                const float d2 = dx * dx + dy * dy;
+                if (d2 > 0.0f && d2 <= R2) orow |= 1ull << (N + k);
+            }
+        }
+        if (!obrow) orow = 0ull;
+        // collisions, contact candidates and the next step's force of agent
+        // rows from the near bits
+        int cc = 0;
+        uint64_t c = 0;
+        bool coincident = false;
+        if (agent) {
+            uint64_t w = near & ~(1ull << li);
+            c = w;
+            const float2 f0 = roll_force<kFmt>(q, anext, true);
+            float Fx = f0.x, Fy = f0.y;
+            const float dmin_aa = q.dmin_aa, dmin_ao = q.dmin_ao;
+            while (w) {
+                const int k = __builtin_ctzll(w);
+                w &= w - 1;
+                const float2 qk = sp[k < N ? k : N + k];
+                const float dx = pm.x - qk.x, dy = pm.y - qk.y;
+                const float d2 = dx * dx + dy * dy;
+                cc += d2 < (k < N ? q.dmin2_aa : q.dmin2_ao) ? 1 : 0;
+                if (d2 == 0.0f) {
+                    c &= ~(1ull << k);
+                    coincident = true;
+                } else {
+                    const float f = contact_scale(q, d2, k < N ? dmin_aa : dmin_ao);
+                    Fx += f * dx;
+                    Fy += f * dy;
+                }
+            }
+            Fn = make_float2(Fx, Fy);
+        }
+        const uint64_t cb = __ballot(coincident);
+        coinc = (h ? (uint32_t)(cb >> 32) : (uint32_t)cb) != 0u;
+        if (__builtin_expect(cb != 0ull, 0)) {
+            // (never seen in practice) the env's rows again with the exact
+            // 0 < d2 <= R2: rad' also holds coincident pairs
+            if (coinc && agent) {
+                uint64_t ex = 0;
+#pragma unroll 1
+                for (int k = 0; k < M; ++k) {
+                    const float2 qk = sp[k < N ? k : N + k];
+                    const float dx = pm.x - qk.x, dy = pm.y - qk.y;
+                    const float d2 = dx * dx + dy * dy;
+                    if (d2 > 0.0f && d2 <= R2) ex |= 1ull << k;
+                }
+                r = ex;
+            }
+            if (coinc && obrow) {
+                const float2 po = sp[2 * N + li];
+                uint64_t ex = 0;
+#pragma unroll 1
+                for (int k = 0; k < N; ++k) {
+                    const float2 qk = sp[k];
+                    const float dx = po.x - qk.x, dy = po.y - qk.y;
+                    const float d2 = dx * dx + dy * dy;
+                    if (d2 > 0.0f && d2 <= R2) ex |= 1ull << k;
+                }
+                orow = (orow & ~(uint64_t)abits) | ex;
+            }
+        }
+        rowa = r;
+        rowo = orow;
+        cand = c;
+        ccnt = cc;
+    };
+    // a lane's list lengths: its agent row (with the edge to its goal) in the
+    // low half, its obstacle row in the high half
+    auto list_word = [&](uint64_t rowa, uint64_t rowo) {
+        return (agent ? __popcll(rowa) + 1 : 0) | (__popcll(rowo) << 16);
+    };
+
+    const uint32_t etag = roll_epoch_tag(epoch);
+    uint8_t deg = 0;
+    // The edges of step t_first + j, emitted two iterations later (the tail:
+    // the last two steps'): positions in buffer pj3, row masks, the inclusive
+    // half scan `inc` of their list words, the workgroup's counts in s_bc[cj3]
+    auto emit_step = [&](const int j, const int pj3, const int cj3, const uint64_t rowa, const uint64_t rowo,
+                         const int inc, const int steps_done) {
+        GSM_REGION("staging");
+        // each env's list staged first (needs only its own row counts): agent
+        // rows, goal rows, obstacle rows
+        const int tot = half_last(inc, h);
+        const int a_total = tot & 0xffff, total = a_total + N + (tot >> 16);
+        int staged = -1;
+        if (env_live && total <= scr_cap) {
+            uint32_t *const scr = (uint32_t *)s_scr;
+            const uint32_t lo = (uint32_t)rowa & abits, hi = (uint32_t)(rowa >> N);
+            if (agent) {
+                uint32_t *at = scr + ((inc & 0xffff) - (__popc(lo) + __popc(hi) + 1));
+                const uint32_t src = (uint32_t)li;
+                for (uint32_t w = lo; w; w &= w - 1) *at++ = src | ((uint32_t)__builtin_ctz(w) << 8);
+                *at++ = src | ((uint32_t)(N + li) << 8);
+                scr[a_total + li] = (uint32_t)(N + li) | ((uint32_t)li << 8);
+                for (uint32_t w = hi; w; w &= w - 1) *at++ = src | ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
+            }
+            if (obrow) {
+                const uint32_t olo = (uint32_t)rowo & abits, ohi = (uint32_t)(rowo >> N);
+                uint32_t *at = scr + (a_total + N + (inc >> 16) - (__popc(olo) + __popc(ohi)));
+                const uint32_t src = (uint32_t)(2 * N + li);
+                for (uint32_t w = olo; w; w &= w - 1) *at++ = src | ((uint32_t)__builtin_ctz(w) << 8);
+                for (uint32_t w = ohi; w; w &= w - 1) *at++ = src | ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
+            }
+            staged = total;
+        }
+        wave_sync();
+        GSM_REGION("prefix");
+        if (wave == 0) {
+            KernargParams &qe = late_params();
+            const uint32_t pv =
+                steps_done > 0 ? __hip_atomic_load(pace_ctr(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            const int cs = qe.roll.csum_stride;
+            const int ex = roll_prefix(qe.roll.gran + (int64_t)j * gridDim.x, qe.roll.csum + (int64_t)j * nc * cs, cs,
+                                       etag | (uint32_t)(j + 1), qe.roll.status, lane);
+            const int lvl = steps_done > 0 ? pace_level((uint32_t)__builtin_amdgcn_readfirstlane(pv), steps_done,
+                                                        __builtin_amdgcn_readfirstlane(s_red[2]), qe.roll.pace_q)
+                                           : 1;
+            if (lane == 0) {
+                s_red[0] = ex;
+                s_red[1] = lvl;
+            }
+        }
+        __syncthreads();
+        GSM_REGION("write");
+        if (steps_done > 0) pace_set(__builtin_amdgcn_readfirstlane(s_red[1]));
+        const int before = s_pre[cj3 * kPairEnvs + slot];
+        const int my_cnt = s_bc[cj3 * kPairEnvs + slot];
+        int64_t env_off = (int64_t)s_red[0] + before;
+        KernargParams &qs = late_params();
+        if (env_off < 0) {   // a broken hand-off: never write out of bounds
+            if (li == 0)
+                __hip_atomic_store((gu32 *)qs.roll.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            env_off = qs.ro.cap;
+        }
+        if (env_live && li == 0) {
+            qs.ro.eptr[b] = env_off;
+            if (b == qs.B - 1) qs.ro.eptr[qs.B] = env_off + my_cnt;
+        }
+        const EdgeSink out = roll_edge_sink<false>(qs, j, K);
+        // the two lists in turn, each written by all 64 lanes
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            if (wb + hh >= qs.B) break;
+            const int st = __builtin_amdgcn_readlane(staged, hh * kPairHalf);
+            const uint32_t off_lo = __builtin_amdgcn_readlane((uint32_t)env_off, hh * kPairHalf);
+            const uint32_t off_hi = __builtin_amdgcn_readlane((uint32_t)((uint64_t)env_off >> 32), hh * kPairHalf);
+            const int64_t off = (int64_t)(((uint64_t)off_hi << 32) | off_lo);
+            const float2 *const s_prev = (const float2 *)(wave_lds + hh * kEnvLds) + pj3 * E;   // positions after step j
+            if (st >= 0 && off + st <= out.cap) {
+                Lane Lw{};
+                Lw.lane = lane;
+                Lw.b = wb + hh;
+                write_staged<kN, kNo>(Lw, s_prev, (const uint32_t *)(wave_lds + hh * kEnvLds + roll_lds_scr(E)), st, off,
+                                      out);
+            } else if (h == hh) {
+                // a list longer than the scratch or than the outputs' rest:
+                // each lane its rows, every store tested
+                const int32_t g0 = (int32_t)((int64_t)b * E);
+                auto put = [&](int64_t at, int32_t a, int32_t d) {
+                    if (at < out.cap) {
+                        const float2 pa = s_prev[a], pd = s_prev[d];
+                        const float dx = pa.x - pd.x, dy = pa.y - pd.y;
+                        out.index[at] = g0 + a;
+                        out.index[out.cap + at] = g0 + d;
+                        out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+                    }
+                };
+                if (agent) {
+                    const uint32_t lo = (uint32_t)rowa & abits, hi = (uint32_t)(rowa >> N);
+                    int64_t o = off + ((inc & 0xffff) - (__popc(lo) + __popc(hi) + 1));
+                    for (uint32_t w = lo; w; w &= w - 1) put(o++, li, __builtin_ctz(w));
+                    put(o++, li, N + li);
+                    for (uint32_t w = hi; w; w &= w - 1) put(o++, li, 2 * N + __builtin_ctz(w));
+                    put(off + a_total + li, N + li, li);
+                }
+                if (obrow) {
+                    const uint32_t olo = (uint32_t)rowo & abits, ohi = (uint32_t)(rowo >> N);
+                    int64_t o = off + a_total + N + ((inc >> 16) - (__popc(olo) + __popc(ohi)));
+                    for (uint32_t w = olo; w; w &= w - 1) put(o++, 2 * N + li, __builtin_ctz(w));
+                    for (uint32_t w = ohi; w; w &= w - 1) put(o++, 2 * N + li, 2 * N + __builtin_ctz(w));
+                }
+            }
+        }
+        wave_sync();
+    };
+
+    GSM_REGION("before the loop");
+    int r3 = 0;                 // k % 3
+    int inc_oo = 0;             // the half scan of the list words of oo_a / oo_o (of the steps of this launch)
+    bool relaid_prev = false;   // the previous iteration re-laid an env of the wave out
+    for (int k = 0; k < K; ++k) {
+        GSM_REGION("integration");
+        const int nrow = arow + 1 == n_act ? 0 : arow + 1;
+        const float4 anext = roll_action_load<kN, kFmt>(late_params(), nrow, eb, ma);
+        const int r3n = r3 == 2 ? 0 : r3 + 1;   // (k + 1) % 3
+        const float2 *const s_cur = pos_buf(r3);
+        float2 *const s_pos = pos_buf(r3n);
+        KernargParams &pc = late_params();
+        if (agent) {
+            const float2 pi = s_cur[li];
+            const float2 F = s_force[li];
+            const float dt = pc.dt;
+            v.x = v.x * pc.omd;
+            v.y = v.y * pc.omd;
+            v.x = v.x + (F.x * pc.inv_mass) * dt;
+            v.y = v.y + (F.y * pc.inv_mass) * dt;
+            float2 np;
+            np.x = pi.x + v.x * dt;
+            np.y = pi.y + v.y * dt;
+            s_pos[li] = np;
+        }
+        wave_sync();
+        t += 1;
+        const bool done = env_live && t >= pc.EL;
+
+        GSM_REGION("sweep");
+        float2 pm = s_pos[ma];
+        uint64_t rowa, rowo, cand;
+        int ccnt;
+        bool coinc;
+        float2 Fn = make_float2(0.0f, 0.0f);
+        sweep(s_pos, pm, false, oo_o, anext, rowa, rowo, cand, ccnt, coinc, Fn);
+
+        GSM_REGION("reward and stores");
+        float r = 0.0f;
+        if (agent) {
+            const float2 g = s_pos[N + li];
+            const float dx = pm.x - g.x, dy = pm.y - g.y;
+            r = -__builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+        }
+        const float rs = half_sum_last(r);
+        const float rs_a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rs), 31));
+        const float rs_b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rs), 63));
+        const float rsum = h ? rs_b : rs_a;
+        const int ci = agent ? ccnt : 0;
+        const int csum = half_last(half_sum_last(ci), h);
+        int scan = half_scan(list_word(rowa, rowo));
+        if (agent) {
+            KernargParams &q = late_params();
+            const uint32_t off = ((uint32_t)eb * (uint32_t)N + (uint32_t)li) * 4u;
+            *(float *)((char *)q.ro.rew + off) = r;
+            *(float *)((char *)q.ro.cost + off) = (float)ci;
+        }
+        if (env_live) {
+            acc.x += rsum;
+            acc.y += (float)csum;
+        }
+        const bool reset = done;   // (auto-reset: the plain configuration)
+        if (reset && li == 0) late_params().ep_last[b] = acc;
+        if (__any(reset)) {
+            // auto-reset: scenario.reset_world for the halves that are done,
+            // then the graph part again (for the wave, applied per half)
+            if (reset) {
+                ep = ep + 1;
+                t = 0;
+                acc = make_float2(0.0f, 0.0f);
+                v = make_float2(0.0f, 0.0f);
+                const uint32_t gid = (uint32_t)(late_params().env_base + b);
+                for (int e = li; e < E; e += kPairHalf) s_pos[e] = layout_pos(p, gid, (uint32_t)ep, (uint32_t)e);
+            }
+            wave_sync();
+            stage_obstacles(s_pos);
+            const float2 pm2 = s_pos[ma];
+            uint64_t rowa2, rowo2, cand2;
+            int cc2;
+            bool coinc2;
+            float2 Fn2 = make_float2(0.0f, 0.0f);
+            sweep(s_pos, pm2, true, 0ull, anext, rowa2, rowo2, cand2, cc2, coinc2, Fn2);
+            if (reset) {
+                pm = pm2;
+                rowa = rowa2;
+                rowo = rowo2;
+                cand = cand2;
+                coinc = coinc2;
+                Fn = Fn2;
+            }
+            scan = half_scan(list_word(rowa, rowo));
+        }
+        const bool relaid = reset;
+        if (agent) s_force[li] = Fn;
+
+        // the step's observation outputs: agent rows every step, goal and
+        // obstacle rows of an env that was re-laid out
+        KernargParams &q = late_params();
+        {
+            float *const nf = q.ro.nf + eb * (E * 7);
+            if (agent) {
+                const float2 g = s_pos[N + li];
+                store_row(nf + li * 7, v, pm, make_float2(g.x - pm.x, g.y - pm.y), 0.0f);
+                if (relaid) store_row(nf + (N + li) * 7, make_float2(0.0f, 0.0f), g, make_float2(0.0f, 0.0f), 1.0f);
+            }
+            if (obrow && relaid)
+                store_row(nf + (2 * N + li) * 7, make_float2(0.0f, 0.0f), s_pos[2 * N + li], make_float2(0.0f, 0.0f),
+                          2.0f);
+        }
+        if (k == K - 1 && q.degenerate) {
+            const uint64_t nb = __ballot(agent && nonfinite2(pm));
+            const bool nfh = (h ? (uint32_t)(nb >> 32) : (uint32_t)nb) != 0u;
+            deg = (uint8_t)((coinc ? kDegCoincident : 0) | (nfh ? kDegNonfinite : 0));
+        }
+        const int tot = half_last(scan, h);
+        const int env_edges = (tot & 0xffff) + (tot >> 16) + (env_live ? N : 0);   // the goal rows: one edge each
+        if (env_live && li == 0) {
+            q.ro.done[b] = done ? 1 : 0;
+            if (k == K - 1) q.ro.ecount[b] = env_edges;
+        }
+
+        GSM_REGION("publish");
+        if (li == 0) s_bc[r3 * kPairEnvs + slot] = env_edges;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int sum = 0, first4 = 0;
+            for (int w = 0; w < kPairEnvs; ++w) {
+                if (w == kWavesPerBlock) first4 = sum;
+                s_pre[r3 * kPairEnvs + w] = sum;
+                sum += s_bc[r3 * kPairEnvs + w];
+            }
+            const int cs = q.roll.csum_stride;
+            prefix_publish(q.roll.gran + (int64_t)k * gridDim.x, q.roll.csum + (int64_t)k * nc * cs, cs,
+                           (int)blockIdx.x, etag | (uint32_t)(k + 1), (uint32_t)sum);
+            // the last step's sums for the emit launch that follows, in the
+            // config's layout of kWavesPerBlock envs per step-kernel workgroup:
+            // two entries per rollout workgroup (the second only if it has envs)
+            if (k == K - 1) {
+                const int rb = (int)blockIdx.x;
+                q.block_edge_sum[2 * rb] = first4;
+                if ((2 * rb + 1) * kWavesPerBlock < q.B) q.block_edge_sum[2 * rb + 1] = sum - first4;
+            }
+        }
+        // the edges of step t - 2
+        if (k >= 2) emit_step(k - 2, r3n == 2 ? 0 : r3n + 1, r3n, s_rowa[lane], s_rowo[lane], (int)s_inc[lane], k);
+        GSM_REGION("loop end");
+        if (threadIdx.x == 0)
+            (void)__hip_atomic_fetch_add(pace_ctr(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == 0) start_prio<1>();
+        // step t - 1's rows for the next iteration's emission, step t's for its sweep
+        s_rowa[lane] = oo_a;
+        s_rowo[lane] = oo_o;
+        s_inc[lane] = (uint32_t)inc_oo;
+        oo_a = rowa;
+        oo_o = rowo;
+        inc_oo = scan;
+        cand_prev = agent ? cand : 0ull;
+        // a re-layout's statics into the other two buffers, each after the
+        // emission that still reads its old ones (gsm_roll_seg_kernel)
+        const bool relaid_now = __any(relaid);
+        if (__builtin_expect(relaid_now || relaid_prev, 0)) {
+            float2 *const dst = pos_buf(r3n == 2 ? 0 : r3n + 1);
+            for (int e = N + li; e < E; e += kPairHalf) dst[e] = s_pos[e];
+        }
+        relaid_prev = relaid_now;
+        arow = nrow;
+        r3 = r3n;
+        wave_sync();
+    }
+    GSM_REGION("after the loop");
+    KernargParams &q = late_params();
+    if (env_live) {
+        float2 *const pos_b = q.pos + eb * E;
+        const float2 *const s_pos = pos_buf(r3);
+        for (int e = li; e < E; e += kPairHalf) pos_b[e] = s_pos[e];
+        if (agent) {
+            (q.vel + eb * N)[li] = v;
+            (q.contact_mask + eb * N)[li] = cand_prev;
+            (q.row_mask + eb * M)[li] = oo_a;
+        }
+        if (obrow) (q.row_mask + eb * M)[N + li] = oo_o;
+        if (li == 0) {
+            q.step_count[b] = t;
+            q.episode[b] = ep;
+            q.ep_acc[b] = acc;
+            if (q.degenerate) q.degenerate[b] = deg;
+        }
+    }
+    {   // the tail: the last two steps' edges (r3 = K % 3), a barrier before
+        // each (wave 0 hands the offset over in s_red[0]: gsm_roll_seg_kernel)
+        const int rm1 = r3 == 0 ? 2 : r3 - 1;   // (K - 1) % 3
+        if (K >= 2) {
+            __syncthreads();
+            emit_step(K - 2, rm1, rm1 == 0 ? 2 : rm1 - 1, s_rowa[lane], s_rowo[lane], (int)s_inc[lane], 0);
+        }
+        __syncthreads();
+        emit_step(K - 1, r3, rm1, oo_a, oo_o, inc_oo, 0);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Fused rollout of SMALL envs (M = N + No <= 16; C2: 3 agents + 3 obstacles),
 // four envs per wave in 16-lane segments. One env per wave left
 // 58 of 64 lanes idle at C2 and paid every per-step wave-level instruction —
@@ -2729,7 +3362,9 @@ bool roll_packed(const DevParams &p) {
 #undef GSM_PICK
     return false;
 }
-int roll_seg_envs_per_block(const DevParams &p) { return roll_packed(p) ? kWavesPerBlock * kPackG : kWavesPerBlock; }
+int roll_seg_envs_per_block(const DevParams &p, bool pair) {
+    return pair ? kPairEnvs : roll_packed(p) ? kWavesPerBlock * kPackG : kWavesPerBlock;
+}
 // the packed small-env rollout with its emission on waves of its own
 // (gsm_roll_pack2_kernel: 512-thread workgroups, two per CU at most, so up to
 // 8192 envs in one residency round; larger batches keep gsm_roll_pack_kernel;
@@ -2757,8 +3392,39 @@ static bool roll_seg_plain(const DevParams &p, bool paced) {
            !(p.max_speed > 0.0f);
 }
 
+// shapes of the two-envs-per-wave rollout (gsm_roll_pair_kernel)
+#define GSM_PAIR_SHAPES(X) X(24, 24)
+// Whether a launch runs gsm_roll_pair_kernel: the plain configuration into the
+// bound buffers, a compiled shape. GSM_ROLL_PAIR=0 keeps the one-env kernel
+// (an A/B knob: the outputs are the same either way).
+bool roll_seg_pair(const DevParams &p, bool slots, bool paced) {
+    static const bool on = [] {
+        const char *e = getenv("GSM_ROLL_PAIR");
+        return !(e && *e && atoi(e) == 0);
+    }();
+    if (!on || slots || p.path != kPathSeg || p.G != 1 || !roll_seg_plain(p, paced)) return false;
+#define GSM_PICK(n, no) if (p.N == n && p.No == no) return true;
+    GSM_PAIR_SHAPES(GSM_PICK)
+#undef GSM_PICK
+    return false;
+}
+
 template <bool kSlots, bool kEager = false>
 static const void *pick_roll_seg(const DevParams &p, bool paced = false) {
+    if constexpr (!kSlots && !kEager) {
+        if (roll_seg_pair(p, false, paced)) {
+#define GSM_PICK(n, no)                                                                       \
+    if (p.N == n && p.No == no) {                                                             \
+        switch (p.action_fmt) {                                                               \
+            case 0: return reinterpret_cast<const void *>(&gsm_roll_pair_kernel<n, no, 0>);   \
+            case 1: return reinterpret_cast<const void *>(&gsm_roll_pair_kernel<n, no, 1>);   \
+            default: return reinterpret_cast<const void *>(&gsm_roll_pair_kernel<n, no, 2>);  \
+        }                                                                                     \
+    }
+            GSM_PAIR_SHAPES(GSM_PICK)
+#undef GSM_PICK
+        }
+    }
     if constexpr (kEager) {   // (one env per wave only: the packed rollout keeps host epochs)
         if (roll_packed(p)) return nullptr;
     } else {
@@ -2813,8 +3479,9 @@ const void *roll_seg_eager_kernel_fn(const DevParams &p) {
     if (p.path != kPathSeg) return nullptr;
     return pick_roll_seg<false, true>(p);
 }
-size_t roll_kernel_lds(const DevParams &p) {
-#define GSM_PICK(n, no)                                                                             \
+size_t roll_kernel_lds(const DevParams &p, bool pair) {
+    if (pair) return (size_t)pair_lds_block(p.N, p.No, p.E);
+#define GSM_PICK(n, no)                                                                            \
     if (p.N == n && p.No == no)                                                                     \
         return roll_pack_split(p) ? (size_t)kWavesPerBlock * pack2_lds_stepper<n, no>() + 4 * kWavesPerBlock * (2 + kPack2Emitters) \
                                   : (size_t)kWavesPerBlock * pack_lds_wave<n, no>() + 4 * kWavesPerBlock;
