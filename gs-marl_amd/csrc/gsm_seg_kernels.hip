@@ -2061,7 +2061,8 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
         const uint64_t cb = __ballot(coincident);
         coinc = (h ? (uint32_t)(cb >> 32) : (uint32_t)cb) != 0u;
         if (__builtin_expect(cb != 0ull, 0)) {
-            // (never seen in practice) the env's rows again with the exact
+            // (no reset layout gets here; test_gpu_roll_states.py's coincident
+            // cases do, at every step) the env's rows again with the exact
             // 0 < d2 <= R2: rad' also holds coincident pairs
             if (coinc && agent) {
                 uint64_t ex = 0;

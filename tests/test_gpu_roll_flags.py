@@ -9,7 +9,10 @@ with several in-launch re-layouts (T > 2 * episode length) and with at least
 three steps (the loop, both tail emissions, and the edge-list scan kept from
 two iterations back). Every case is compared bit for bit, over every state and
 output buffer, with the per-step chain of the same actions (step kernels and
-emit kernel: other code than the rollout kernel). Also the rollout-buffer form
+emit kernel: other code than the rollout kernel). (A reset layout holds no
+coincident pair, so the strict case runs the strict instantiation on inputs
+where it equals the default; test_gpu_roll_states.py runs it on coincident
+pairs, NaN bits compared.) Also the rollout-buffer form
 (per-step redirected outputs), the one-launch eager step, and one case against
 the fp64 CPU oracle."""
 import numpy as np
