@@ -1524,6 +1524,73 @@ int gsm_attn_aggregate_bwd(const float *grad_out, const float *q, const float *k
     return GSM_OK;
 }
 
+static int graph_batch_shape(int64_t n_slots, int64_t n_envs, int64_t edge_capacity, int64_t n_samples) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_samples < 0 || n_samples >= lim) return fail(nullptr, GSM_EINVAL, "n_samples must be in [0, 2^31)");
+    if (n_slots < 1 || n_slots >= lim || n_envs < 1 || n_envs >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_slots and n_envs must be in [1, 2^31)");
+    if (edge_capacity < 0 || edge_capacity >= lim)
+        return fail(nullptr, GSM_EINVAL, "edge_capacity must be in [0, 2^31)");
+    return GSM_OK;
+}
+
+int gsm_graph_batch_ptr(const int64_t *edge_ptr, int64_t n_slots, int64_t n_envs, int64_t edge_capacity,
+                        const int64_t *t_idx, const int64_t *b_idx, int64_t n_samples, int64_t *sample_ptr,
+                        int32_t *status, void *stream) {
+    if (const int rc = graph_batch_shape(n_slots, n_envs, edge_capacity, n_samples)) return rc;
+    if (!sample_ptr || !status) return fail(nullptr, GSM_EINVAL, "sample_ptr or status is NULL");
+    if (n_samples > 0 && (!edge_ptr || !t_idx || !b_idx))
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    const hipError_t e = gsm::launch_graph_batch_ptr(edge_ptr, n_slots, n_envs, edge_capacity, t_idx, b_idx,
+                                                     n_samples, sample_ptr, status, as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_graph_batch_ptr launch");
+    return GSM_OK;
+}
+
+int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, const float *edge_attr,
+                           const int64_t *edge_ptr, int64_t n_slots, int64_t n_envs, int32_t n_entities,
+                           int64_t edge_capacity, const int64_t *t_idx, const int64_t *b_idx,
+                           const int64_t *sample_ptr, int64_t n_samples, int64_t n_edges, float *node_feat_out,
+                           int64_t *row_ptr, int32_t *col, float *edge_attr_out, int32_t *t_edge,
+                           int32_t *status, void *stream) {
+    if (const int rc = graph_batch_shape(n_slots, n_envs, edge_capacity, n_samples)) return rc;
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_entities < 1 || n_samples * n_entities >= lim || n_envs * n_entities >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_entities >= 1; n_samples*n_entities and n_envs*n_entities < 2^31");
+    if (n_edges < 0 || n_edges >= lim) return fail(nullptr, GSM_EINVAL, "n_edges must be in [0, 2^31)");
+    if (!row_ptr || !status) return fail(nullptr, GSM_EINVAL, "row_ptr or status is NULL");
+    if (n_samples > 0 && (!node_feat || !edge_index || !edge_attr || !edge_ptr || !t_idx || !b_idx ||
+                          !sample_ptr || !node_feat_out))
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    if (n_edges > 0 && (!col || !edge_attr_out)) return fail(nullptr, GSM_EINVAL, "col or edge_attr_out is NULL");
+    if (n_samples == 0 && n_edges > 0) return fail(nullptr, GSM_EINVAL, "edges without samples");
+    hipStream_t s = as_stream(stream);
+    if (n_samples == 0) {
+        const hipError_t e = hipMemsetAsync(row_ptr, 0, sizeof(int64_t), s);
+        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_graph_batch_gather memset");
+        return GSM_OK;
+    }
+    const hipError_t e = gsm::launch_graph_batch_gather(node_feat, edge_index, edge_attr, edge_ptr, n_slots, n_envs,
+                                                        n_entities, edge_capacity, t_idx, b_idx, sample_ptr,
+                                                        n_samples, n_edges, node_feat_out, row_ptr, col,
+                                                        edge_attr_out, t_edge, status, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_graph_batch_gather launch");
+    return GSM_OK;
+}
+
+int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
+            int32_t n_agents, float gamma, float gamma_lambda, float *ret, void *stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_steps < 1 || n_steps >= lim) return fail(nullptr, GSM_EINVAL, "n_steps must be in [1, 2^31)");
+    if (n_envs < 1 || n_agents < 1 || n_envs >= lim || n_envs * n_agents >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_envs, n_agents >= 1 and n_envs*n_agents < 2^31");
+    if (!reward || !value || !done || !ret) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    const hipError_t e = gsm::launch_gae(reward, value, done, n_steps, n_envs, n_agents, gamma, gamma_lambda, ret,
+                                         as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_gae launch");
+    return GSM_OK;
+}
+
 int gsm_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,
                const int32_t *edge_index, int64_t edge_capacity, const int32_t *env_ids, int32_t n_frames,
                float half_width, float agent_size, float target_size, float obstacle_size, int32_t width,

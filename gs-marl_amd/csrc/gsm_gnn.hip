@@ -21,6 +21,7 @@
 // shuffles; an online softmax keeps (max, denominator, accumulator) in
 // registers while the row's edges stream through (the next edge's index one
 // iteration ahead), so every k_j / v_j row is read once per edge.
+#include "gsm.h"
 #include "gsm_device.h"
 
 namespace gsm {
@@ -470,6 +471,273 @@ hipError_t launch_attn_backward(const float *g, const float *q, const float *k, 
     }
 #undef GSM_ATTN_BWD
     if (dw_e) gsm_attn_bwd_dwe_kernel<<<1, 64 * kBwdSumRows, 0, s>>>(part, (int)blocks_a, HC, dw_e);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Minibatch assembly: K samples (slot t_k, env b_k) of a rollout buffer as one
+// CSR batch with its transposed graph, for the kernels above. Two launches
+// with the per-sample entry offsets handed over the kernel boundary:
+//
+//   ptr kernel     cnt_k = edge_ptr[t_k][b_k+1] - edge_ptr[t_k][b_k] (0 for a
+//                  bad sample), sample_ptr = exclusive scan; one workgroup,
+//                  kPtrItems consecutive samples per thread and chunk, their
+//                  loads issued together
+//   gather kernel  one wave per sample: node rows copied; a node's row offset
+//                  is the lower bound of its id in the sample's (sorted)
+//                  source list; columns relabelled b*E + e -> k*E + e; and,
+//                  the env graph being symmetric with ascending rows and
+//                  columns, the transposed CSR is (row_ptr, t_edge, col) with
+//                  t_edge[p] = the position of row(p) inside row col(p): one
+//                  more search
+//
+// Every offset read from memory is checked before it bounds a loop or forms an
+// address: a sample's range must satisfy 0 <= start <= end <= capacity (else it
+// counts no entries) and its output range must lie inside [0, n_edges) with the
+// same length (else nothing is written for it); every search runs over the
+// sample's own entries only. Bad data sets status bits and gets defined
+// in-range values.
+
+constexpr int kPtrThreads = 1024;
+constexpr int kPtrItems = 8;          // samples per thread and chunk
+constexpr int kStageEntries = 512;    // entries per wave staged in LDS (src and dst: 4 KiB a wave)
+
+// the checked entry range of sample (t, b): false (and bits) when it is unusable
+__device__ __forceinline__ bool sample_range(const int64_t *__restrict__ edge_ptr, int64_t S, int64_t B,
+                                             int64_t cap, int64_t t, int64_t b, int64_t &start, int64_t &cnt,
+                                             int &bits) {
+    start = 0;
+    cnt = 0;
+    if (t < 0 || t >= S || b < 0 || b >= B) {
+        bits |= GSM_BATCH_BAD_INDEX;
+        return false;
+    }
+    const int64_t a = edge_ptr[t * (B + 1) + b], e = edge_ptr[t * (B + 1) + b + 1];
+    if (e > cap) {
+        bits |= GSM_BATCH_TRUNCATED;
+        return false;
+    }
+    if (a < 0 || e < a) {
+        bits |= GSM_BATCH_BAD_OFFSETS;
+        return false;
+    }
+    start = a;
+    cnt = e - a;
+    return true;
+}
+
+__global__ __launch_bounds__(kPtrThreads) void gsm_graph_batch_ptr_kernel(
+    const int64_t *__restrict__ edge_ptr, int64_t S, int64_t B, int64_t cap, const int64_t *__restrict__ t_idx,
+    const int64_t *__restrict__ b_idx, int64_t K, int64_t *__restrict__ sample_ptr, int32_t *__restrict__ status) {
+    __shared__ int64_t wsum[kPtrThreads / kWave];
+    __shared__ int64_t chunk_total;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int bits = 0;
+    int64_t carry = 0;
+    if (tid == 0) sample_ptr[0] = 0;
+    for (int64_t base = 0; base < K; base += (int64_t)kPtrThreads * kPtrItems) {
+        const int64_t k0 = base + (int64_t)tid * kPtrItems;
+        int64_t t[kPtrItems], b[kPtrItems], cnt[kPtrItems];
+#pragma unroll
+        for (int u = 0; u < kPtrItems; ++u) {
+            const bool in = k0 + u < K;
+            t[u] = in ? t_idx[k0 + u] : -1;
+            b[u] = in ? b_idx[k0 + u] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < kPtrItems; ++u) {
+            int64_t start;
+            cnt[u] = 0;
+            if (k0 + u < K) sample_range(edge_ptr, S, B, cap, t[u], b[u], start, cnt[u], bits);
+        }
+        int64_t mine = 0;
+#pragma unroll
+        for (int u = 0; u < kPtrItems; ++u) mine += cnt[u];
+        int64_t inc = mine;                                   // inclusive scan over the wave
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const int64_t up = __shfl_up(inc, o);
+            if (lane >= o) inc += up;
+        }
+        if (lane == kWave - 1) wsum[wv] = inc;
+        __syncthreads();
+        int64_t before = 0;
+        for (int w = 0; w < wv; ++w) before += wsum[w];
+        if (tid == kPtrThreads - 1) chunk_total = before + inc;
+        int64_t run = carry + before + inc - mine;            // entries before this thread's samples
+#pragma unroll
+        for (int u = 0; u < kPtrItems; ++u) {
+            run += cnt[u];
+            if (k0 + u < K) sample_ptr[k0 + u + 1] = run;
+        }
+        __syncthreads();
+        carry += chunk_total;
+    }
+    if (bits) atomicOr(status, bits);
+}
+
+// first position in [0, n) whose value is >= x (n when none); the list ascends
+template <class A>
+__device__ __forceinline__ int lower_bound(const A &at, int lo, int n, int x) {
+    int hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (at(mid) < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the sample's entries through src(p), dst(p): local ids (global id - b*E)
+template <class FS, class FD>
+__device__ __forceinline__ void batch_sample_entries(const FS &src, const FD &dst, int n, int E, int lane,
+                                                     int64_t k, int64_t s0, const float *__restrict__ attr_in,
+                                                     int64_t *__restrict__ row_ptr, int32_t *__restrict__ col,
+                                                     float *__restrict__ attr_out, int32_t *__restrict__ t_edge,
+                                                     int &bits) {
+    for (int e = lane; e < E; e += kWave) row_ptr[k * E + e] = s0 + lower_bound(src, 0, n, e);
+    for (int p = lane; p < n; p += kWave) {
+        const int j = src(p), i = dst(p);
+        const bool inside = i >= 0 && i < E && j >= 0 && j < E;
+        if (!inside) bits |= GSM_BATCH_OUT_OF_ENV;
+        col[s0 + p] = (int32_t)(k * E + min(max(i, 0), E - 1));
+        attr_out[s0 + p] = attr_in[p];
+        if (t_edge) {
+            int q = p;
+            if (inside) {
+                // row i of the sample, then j's position among its columns
+                const int r0 = lower_bound(src, 0, n, i);
+                const int r1 = lower_bound(src, r0, n, i + 1);
+                const int f = lower_bound(dst, r0, r1, j);
+                if (f < r1 && dst(f) == j && src(f) == i) q = f;
+                else bits |= GSM_BATCH_ASYMMETRIC;
+            }
+            t_edge[s0 + p] = (int32_t)(s0 + q);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gsm_graph_batch_gather_kernel(
+    const float *__restrict__ node_feat, const int32_t *__restrict__ edge_index,
+    const float *__restrict__ edge_attr, const int64_t *__restrict__ edge_ptr, int64_t S, int64_t B, int E,
+    int64_t cap, const int64_t *__restrict__ t_idx, const int64_t *__restrict__ b_idx,
+    const int64_t *__restrict__ sample_ptr, int64_t K, int64_t n_edges, float *__restrict__ node_feat_out,
+    int64_t *__restrict__ row_ptr, int32_t *__restrict__ col, float *__restrict__ attr_out,
+    int32_t *__restrict__ t_edge, int32_t *__restrict__ status) {
+    __shared__ int32_t lsrc[4][kStageEntries], ldst[4][kStageEntries];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t k = (int64_t)blockIdx.x * 4 + wv;           // wave-uniform
+    const bool have = k < K;
+    int bits = 0, n = 0;
+    int64_t t = 0, b = 0, start = 0, s0 = 0;
+    bool valid = false;
+    if (have) {
+        int64_t cnt;
+        t = t_idx[k];
+        b = b_idx[k];
+        valid = sample_range(edge_ptr, S, B, cap, t, b, start, cnt, bits);
+        if (!valid) t = b = 0;
+        s0 = sample_ptr[k];
+        const int64_t s1 = sample_ptr[k + 1];
+        // the scan's range must be this sample's count inside the outputs
+        if (s0 < 0 || s1 < s0 || s1 > n_edges || s1 - s0 != cnt) {
+            bits |= GSM_BATCH_BAD_OFFSETS;
+            cnt = 0;
+            s0 = min(max(s0, (int64_t)0), n_edges);
+        }
+        n = (int)cnt;                                         // <= n_edges < 2^31
+    }
+    const int32_t *gs = edge_index + (valid ? (t * 2 * cap + start) : 0), *gd = gs + cap;
+    const int bE = (int)(b * E);                              // K*E and B*E < 2^31 (host-checked)
+    const bool staged = n <= kStageEntries;
+    if (staged)
+        for (int p = lane; p < n; p += kWave) {
+            lsrc[wv][p] = gs[p] - bE;
+            ldst[wv][p] = gd[p] - bE;
+        }
+    __syncthreads();
+    if (!have) return;
+    // node rows: E*7 dwords, contiguous on both sides; 16-byte pieces when aligned
+    {
+        const int nd = E * 7;
+        const float *in = node_feat + (valid ? (t * B + b) * nd : 0);
+        float *out = node_feat_out + k * nd;
+        if (!valid) {
+            for (int x = lane; x < nd; x += kWave) out[x] = 0.0f;
+        } else if (((uintptr_t)in | (uintptr_t)out) % 16 == 0 && nd % 4 == 0) {
+            for (int x = lane; x < nd / 4; x += kWave) ((float4 *)out)[x] = ((const float4 *)in)[x];
+        } else {
+            for (int x = lane; x < nd; x += kWave) out[x] = in[x];
+        }
+    }
+    if (k == K - 1 && lane == 0) row_ptr[K * E] = n_edges;
+    const float *attr_in = edge_attr + (valid ? (t * cap + start) : 0);
+    if (staged) {
+        const int32_t *ls = lsrc[wv], *ld = ldst[wv];
+        batch_sample_entries([ls](int p) { return ls[p]; }, [ld](int p) { return ld[p]; }, n, E, lane, k, s0,
+                             attr_in, row_ptr, col, attr_out, t_edge, bits);
+    } else {
+        batch_sample_entries([gs, bE](int p) { return gs[p] - bE; }, [gd, bE](int p) { return gd[p] - bE; }, n, E,
+                             lane, k, s0, attr_in, row_ptr, col, attr_out, t_edge, bits);
+    }
+    if (bits) atomicOr(status, bits);
+}
+
+hipError_t launch_graph_batch_ptr(const int64_t *edge_ptr, int64_t S, int64_t B, int64_t cap,
+                                  const int64_t *t_idx, const int64_t *b_idx, int64_t K, int64_t *sample_ptr,
+                                  int32_t *status, hipStream_t s) {
+    (void)hipGetLastError();
+    gsm_graph_batch_ptr_kernel<<<1, kPtrThreads, 0, s>>>(edge_ptr, S, B, cap, t_idx, b_idx, K, sample_ptr, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_graph_batch_gather(const float *node_feat, const int32_t *edge_index, const float *edge_attr,
+                                     const int64_t *edge_ptr, int64_t S, int64_t B, int E, int64_t cap,
+                                     const int64_t *t_idx, const int64_t *b_idx, const int64_t *sample_ptr,
+                                     int64_t K, int64_t n_edges, float *node_feat_out, int64_t *row_ptr,
+                                     int32_t *col, float *attr_out, int32_t *t_edge, int32_t *status,
+                                     hipStream_t s) {
+    (void)hipGetLastError();
+    gsm_graph_batch_gather_kernel<<<(unsigned)((K + 3) / 4), 256, 0, s>>>(
+        node_feat, edge_index, edge_attr, edge_ptr, S, B, E, cap, t_idx, b_idx, sample_ptr, K, n_edges,
+        node_feat_out, row_ptr, col, attr_out, t_edge, status);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// GAE over a stored episode: one thread per (env, agent) walks the slots from
+// the last to the first with the running advantage in a register; the loads
+// of a slot are coalesced across (env, agent). Each operation below is one
+// correctly rounded fp32 operation in the order of the torch loop it replaces
+// (the library is built with -ffp-contract=off), so the returns are the same
+// bit for bit.
+__global__ __launch_bounds__(256) void gsm_gae_kernel(const float *__restrict__ reward,
+                                                      const float *__restrict__ value,
+                                                      const uint8_t *__restrict__ done, int64_t T, int64_t BN,
+                                                      int N, float gamma, float gamma_lambda,
+                                                      float *__restrict__ ret) {
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= BN) return;
+    const int64_t B = (uint32_t)BN / (uint32_t)N, b = (uint32_t)x / (uint32_t)N;   // B*N < 2^31 (host-checked)
+    float gae = 0.0f;
+    float v1 = value[T * BN + x];
+#pragma unroll 4
+    for (int64_t t = T - 1; t >= 0; --t) {
+        const float r = reward[t * BN + x], v0 = value[t * BN + x];
+        const float m = 1.0f - (float)done[(t + 1) * B + b];
+        const float delta = (r + (gamma * v1) * m) - v0;
+        gae = delta + (gamma_lambda * m) * gae;
+        ret[t * BN + x] = gae + v0;
+        v1 = v0;
+    }
+}
+
+hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
+                      float gamma, float gamma_lambda, float *ret, hipStream_t s) {
+    const int64_t BN = B * N;
+    (void)hipGetLastError();
+    gsm_gae_kernel<<<(unsigned)((BN + 255) / 256), 256, 0, s>>>(reward, value, done, T, BN, N, gamma,
+                                                                gamma_lambda, ret);
     return hipGetLastError();
 }
 

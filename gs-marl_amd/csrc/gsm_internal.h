@@ -276,6 +276,18 @@ hipError_t launch_attn_backward(const float *g, const float *q, const float *k, 
                                 const int64_t *t_ptr, const int32_t *t_edge, const int32_t *t_tgt,
                                 int64_t n_nodes, int64_t n_edges, int HC, int C, float scale, float *work,
                                 float *dq, float *dk, float *dv, float *dedge_w, float *dw_e, hipStream_t s);
+// minibatch assembly (gsm_gnn.hip): sample entry offsets, then the CSR batch
+hipError_t launch_graph_batch_ptr(const int64_t *edge_ptr, int64_t S, int64_t B, int64_t cap,
+                                  const int64_t *t_idx, const int64_t *b_idx, int64_t K, int64_t *sample_ptr,
+                                  int32_t *status, hipStream_t s);
+hipError_t launch_graph_batch_gather(const float *node_feat, const int32_t *edge_index, const float *edge_attr,
+                                     const int64_t *edge_ptr, int64_t S, int64_t B, int E, int64_t cap,
+                                     const int64_t *t_idx, const int64_t *b_idx, const int64_t *sample_ptr,
+                                     int64_t K, int64_t n_edges, float *node_feat_out, int64_t *row_ptr,
+                                     int32_t *col, float *attr_out, int32_t *t_edge, int32_t *status,
+                                     hipStream_t s);
+hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
+                      float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,
                          const int32_t *edge_index, int64_t edge_capacity, const int32_t *env_ids,
                          int32_t n_frames, float half_width, float r_agent, float r_target, float r_obst,

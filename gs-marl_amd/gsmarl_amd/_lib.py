@@ -20,6 +20,7 @@ GRAPH_STEP, GRAPH_EMIT, GRAPH_TIME_EACH, GRAPH_TIME_ENDS = 1, 2, 4, 8
 GRAPH_UNFUSED, GRAPH_LAG_ONLY, GRAPH_ROLL = 16, 32, 64
 RENDER_EDGES = 1
 ACT_ONEHOT, ACT_INDEX, ACT_CONT = 0, 1, 2
+BATCH_BAD_INDEX, BATCH_TRUNCATED, BATCH_BAD_OFFSETS, BATCH_OUT_OF_ENV, BATCH_ASYMMETRIC = 1, 2, 4, 8, 16
 
 
 class GsmConfig(C.Structure):
@@ -103,6 +104,10 @@ SIGNATURES = {
                                                 C.POINTER(C.c_int64)]),
     "gsm_attn_aggregate_bwd": (C.c_int, [_P] * 14 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float] +
                                [_P] * 7),
+    "gsm_graph_batch_ptr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
+    "gsm_graph_batch_gather": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P,
+                                         C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "gsm_gae": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "gsm_render": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gsm_debug_set_stamps": (C.c_int, [_P, _P]),

@@ -16,7 +16,11 @@ restates that layer:
 * ``attn_aggregate_autograd`` is the kernel with gradients (the HIP backward
   ``gsm_attn_aggregate_bwd`` over the CSR rows and the transposed graph of
   ``csr_transpose``; ``attn_aggregate_bwd_ref`` is its torch restatement), which
-  ``TransformerConv(kernel_backward=True)`` trains on.
+  ``TransformerConv(kernel_backward=True)`` trains on;
+* ``csr_transpose_symmetric`` is that transposed graph without the sort, for
+  symmetric graphs with ascending rows and columns such as the env's: the
+  formulation ``GraphRolloutBuffer.graph_batch_csr``'s gather kernel
+  (``gsm_graph_batch_gather``) is written against.
 
 Graph format: CSR over targets (``row_ptr`` [n+1] int64, ``col`` int32
 sources, ``edge_w`` per CSR entry). The env graphs are symmetric (every radius
@@ -134,6 +138,33 @@ def csr_transpose(row_ptr, col):
     torch.cumsum(torch.bincount(src, minlength=n), 0, out=t_ptr[1:])
     tgt = torch.repeat_interleave(torch.arange(n, device=dev), row_ptr[1:] - row_ptr[:-1], output_size=nE)
     return t_ptr, perm.to(torch.int32), tgt[perm].to(torch.int32)
+
+
+def csr_transpose_symmetric(row_ptr, col):
+    """``csr_transpose`` without the sort, for a symmetric graph whose columns
+    ascend without duplicates inside every row (the env's graphs):
+    there ``t_ptr == row_ptr`` and ``t_tgt == col``, and for entry ``p`` in row
+    ``j`` with column ``i``, ``t_edge[p]`` is the position of ``j`` inside row
+    ``i``: one ``searchsorted`` of the reverse keys ``i*n + j`` in the row-major
+    keys ``j*n + i`` (which ascend). Returns ``(t_ptr, t_edge, t_tgt, ok)``,
+    ``ok`` a bool tensor per entry: its reverse entry was found (where it is
+    missing, ``t_edge[p] = p``, so every index stays in range). Plain
+    torch on any device: the formulation ``gsm_graph_batch_gather`` is written
+    against."""
+    n, nE = row_ptr.numel() - 1, col.numel()
+    dev = col.device
+    t_tgt = col.to(torch.int32)
+    if nE == 0 or n == 0:
+        return (row_ptr, torch.zeros(0, dtype=torch.int32, device=dev), t_tgt,
+                torch.ones(0, dtype=torch.bool, device=dev))
+    src = col.to(torch.int64)
+    tgt = torch.repeat_interleave(torch.arange(n, device=dev), row_ptr[1:] - row_ptr[:-1], output_size=nE)
+    keys = tgt * n + src
+    rev = src * n + tgt
+    pos = torch.searchsorted(keys, rev).clamp_(max=nE - 1)
+    ok = keys[pos] == rev
+    t_edge = torch.where(ok, pos, torch.arange(nE, device=dev)).to(torch.int32)
+    return row_ptr, t_edge, t_tgt, ok
 
 
 def _check_kernel_inputs(q, k, v, row_ptr, col, edge_w, w_e, what):

@@ -29,14 +29,24 @@ headline density); a slot whose ``edge_ptr[B]`` exceeds it has its edges
 truncated (``overflowed()`` reports it), never written out of bounds.
 ``graph_batch`` assembles a PyG-style batch of (t, b) samples for the
 minibatch generators; ``compute_returns`` is GAE over rewards or costs.
+``graph_batch_csr`` assembles the same samples as the CSR batch (with its
+transposed graph) the attention kernels take, in two HIP launches
+(``gsm_graph_batch_ptr`` / ``gsm_graph_batch_gather``), and
+``compute_returns(kernel=True)`` is the GAE loop as one launch (``gsm_gae``).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import torch
 
+from . import _lib
 from .batch import GpuBatchEnv
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
 class GraphRolloutBuffer:
@@ -189,6 +199,80 @@ class GraphRolloutBuffer:
                     batch=torch.arange(K, device=t.device).repeat_interleave(E),
                     ptr=ptr)
 
+    def graph_batch_csr(self, t_idx: torch.Tensor, b_idx: torch.Tensor, transpose: bool = True,
+                        check: bool = True) -> dict:
+        """The samples of ``graph_batch`` as the CSR batch the attention kernels
+        take, assembled by two HIP launches (gsm_graph_batch_ptr,
+        gsm_graph_batch_gather): node_feat [K*E, 7], row_ptr int64 [K*E+1], col
+        int32 [sum] (local ids k*E + e), edge_attr [sum], ptr [K+1] (the
+        samples' entry offsets), status (device int32 [1], GSM_BATCH_* bits) and
+        ``transpose`` = (row_ptr, t_edge, col), the transposed graph for
+        ``attn_aggregate_autograd`` / ``TransformerConv.forward(transpose=...)``
+        (None with ``transpose=False``): ``gnn.csr_transpose`` of the batch
+        without its sort, since the env's graphs are symmetric with ascending
+        rows and columns. One host synchronisation reads the entry total that
+        sizes the outputs, and with it the first launch's status: IndexError for
+        an out-of-range index, ValueError for a sample whose slot overflowed
+        the edge capacity. With ``check`` a second one reads the gather's status
+        (RuntimeError for an entry outside its env or without its reverse
+        entry); without, the caller has ``status``."""
+        self.validate()
+        E, dev = self.E, self.edge_ptr.device
+        t = t_idx.to(dev, torch.int64).contiguous()
+        b = b_idx.to(dev, torch.int64).contiguous()
+        K = t.numel()
+        if b.numel() != K:
+            raise ValueError("graph_batch_csr: t_idx and b_idx differ in length")
+        i32, i64 = torch.int32, torch.int64
+        if K == 0:
+            row_ptr, col = torch.zeros(1, dtype=i64, device=dev), torch.zeros(0, dtype=i32, device=dev)
+            return dict(node_feat=self.node_feat.new_zeros(0, 7), row_ptr=row_ptr, col=col,
+                        edge_attr=self.edge_attr.new_zeros(0), ptr=torch.zeros(1, dtype=i64, device=dev),
+                        transpose=(row_ptr, torch.zeros(0, dtype=i32, device=dev), col) if transpose else None,
+                        status=torch.zeros(1, dtype=i32, device=dev))
+        lib = _lib.load()
+        S, B = self.T + 1, self.B
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        # sample offsets [K+1] and the status word in one allocation: its last
+        # two words come back in one copy
+        head = torch.zeros(K + 2, dtype=i64, device=dev)
+        ptr, status = head[:K + 1], head[K + 1:].view(i32)[:1]
+        _lib.check(lib, lib.gsm_graph_batch_ptr(_ptr(self.edge_ptr), S, B, self.cap, _ptr(t), _ptr(b), K, _ptr(ptr),
+                                                _ptr(status), stream), None, "gsm_graph_batch_ptr")
+        total, st = head[K:].cpu().tolist()
+        st &= 0xFFFFFFFF
+        if st & _lib.BATCH_BAD_INDEX:
+            raise IndexError(f"graph_batch_csr: a sample's slot is outside [0, {S}) or its env outside [0, {B})")
+        if st & _lib.BATCH_TRUNCATED:
+            raise ValueError(f"graph_batch_csr: a requested sample's edges run past the slot capacity {self.cap} "
+                             "(the slot overflowed and was truncated); size the buffer with a larger edge "
+                             "capacity")
+        if st:
+            raise RuntimeError("graph_batch_csr: a requested sample's edge offsets are corrupt (end < start)")
+        if total >= 2 ** 31 or K * E >= 2 ** 31:
+            raise ValueError("graph_batch_csr: the batch needs fewer than 2^31 nodes and entries")
+        node_feat = torch.empty(K * E, 7, dtype=torch.float32, device=dev)
+        row_ptr = torch.empty(K * E + 1, dtype=i64, device=dev)
+        col = torch.empty(total, dtype=i32, device=dev)
+        edge_attr = torch.empty(total, dtype=torch.float32, device=dev)
+        t_edge = torch.empty(total, dtype=i32, device=dev) if transpose else None
+        rc = lib.gsm_graph_batch_gather(_ptr(self.node_feat), _ptr(self.edge_index), _ptr(self.edge_attr),
+                                        _ptr(self.edge_ptr), S, B, E, self.cap, _ptr(t), _ptr(b), _ptr(ptr), K, total,
+                                        _ptr(node_feat), _ptr(row_ptr), _ptr(col), _ptr(edge_attr), _ptr(t_edge),
+                                        _ptr(status), stream)
+        _lib.check(lib, rc, None, "gsm_graph_batch_gather")
+        if check:
+            st = int(status.item())
+            if st:
+                what = [w for bit, w in ((_lib.BATCH_OUT_OF_ENV, "an entry's node id lies outside its env"),
+                                         (_lib.BATCH_ASYMMETRIC, "an entry's reverse entry is missing (the graph "
+                                                                 "is not symmetric with ascending columns)"),
+                                         (_lib.BATCH_BAD_OFFSETS, "the sample offsets do not match the slots"))
+                        if st & bit]
+                raise RuntimeError(f"graph_batch_csr: the stored graph is invalid (status {st}): " + "; ".join(what))
+        return dict(node_feat=node_feat, row_ptr=row_ptr, col=col, edge_attr=edge_attr, ptr=ptr,
+                    transpose=(row_ptr, t_edge, col) if transpose else None, status=status)
+
     def render(self, env: int = 0, slots=None, width: int = 700, height: int = 700,
                edges: bool = True) -> torch.Tensor:
         """Frames uint8 [len(slots), H, W, 3] of env ``env`` over the stored
@@ -203,10 +287,24 @@ class GraphRolloutBuffer:
         return torch.cat(frames)
 
     def compute_returns(self, values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
-                        which: str = "reward") -> torch.Tensor:
+                        which: str = "reward", kernel: bool = False) -> torch.Tensor:
         """GAE returns [T, B, N] of the rewards (or costs, for the safe-RL
-        cost critic) given value predictions values [T+1, B, N]."""
+        cost critic) given value predictions values [T+1, B, N]. With
+        ``kernel`` the loop below runs as one HIP launch (gsm_gae), bit for bit
+        the same returns."""
         r = self.rewards if which == "reward" else self.costs
+        if kernel:
+            if values.shape != (self.T + 1, self.B, self.N) or values.device != r.device:
+                raise ValueError(f"values: need [{self.T + 1}, {self.B}, {self.N}] on {r.device}")
+            v = values.to(torch.float32).contiguous()
+            ret = torch.empty_like(r)
+            lib = _lib.load()
+            stream = C.c_void_p(torch.cuda.current_stream(r.device).cuda_stream)
+            # gamma * gae_lambda: the double product, rounded once to fp32 as the loop's scalar is
+            rc = lib.gsm_gae(_ptr(r), _ptr(v), _ptr(self.done), self.T, self.B, self.N, float(gamma),
+                             float(gamma * gae_lambda), _ptr(ret), stream)
+            _lib.check(lib, rc, None, "gsm_gae")
+            return ret
         masks = self.masks
         ret = torch.empty_like(r)
         gae = torch.zeros_like(r[0])

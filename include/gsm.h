@@ -389,6 +389,70 @@ int gsm_attn_aggregate_bwd(const float *grad_out, const float *q, const float *k
                            int32_t heads, int32_t channels, float scale, float *work, float *dq, float *dk,
                            float *dv, float *dedge_w, float *dw_e, void *stream);
 
+/* Minibatch assembly from a rollout buffer (the
+ * reader side): K samples (slot t_idx[k], env b_idx[k]) of stored env graphs
+ * as one CSR batch for gsm_attn_aggregate*, with the transposed graph the
+ * backward wants. The buffer: edge_ptr int64 [n_slots][n_envs+1] (per-slot CSR
+ * offsets), edge_index int32 [n_slots][2][edge_capacity] (global ids
+ * b*n_entities + e, rows in ascending source order), edge_attr f32
+ * [n_slots][edge_capacity], node_feat f32 [n_slots][n_envs][n_entities][7].
+ *
+ * gsm_graph_batch_ptr (one launch, one workgroup): sample_ptr int64
+ * [n_samples+1] = exclusive scan of the samples' entry counts. A sample whose
+ * indices are out of range, whose slot range runs past edge_capacity (a
+ * truncated slot) or whose offsets are not 0 <= start <= end counts 0 entries
+ * and ORs a bit into status (device int32 [1], zeroed by the caller).
+ *
+ * gsm_graph_batch_gather (one launch, one wave per sample; n_edges =
+ * sample_ptr[n_samples], read back by the caller to size the outputs):
+ *   node_feat_out f32 [n_samples*n_entities][7]  the samples' rows, bit for bit
+ *   row_ptr int64 [n_samples*n_entities+1]       per-node offsets (a node's is
+ *                                                the lower bound of its id in
+ *                                                the sample's source list)
+ *   col int32 [n_edges]                          targets' column ids relabelled
+ *                                                b*E + e -> k*E + e
+ *   edge_attr_out f32 [n_edges]
+ *   t_edge int32 [n_edges], or NULL              for entry p in row j with column
+ *                                                i: the position of j inside row
+ *                                                i (a binary search)
+ * For the env's graphs (symmetric, columns ascending without duplicates inside
+ * a row) the transposed CSR of gsm_attn_aggregate_bwd is t_ptr = row_ptr,
+ * t_edge, t_tgt = col. An entry with an id outside its env's [b*E, (b+1)*E)
+ * sets GSM_BATCH_OUT_OF_ENV and gets its column clamped into the sample; one
+ * whose reverse entry is missing sets GSM_BATCH_ASYMMETRIC; both get t_edge[p]
+ * = p. The offsets are checked again here (a sample whose sample_ptr range is
+ * not its entry count inside [0, n_edges] writes no entries and sets
+ * GSM_BATCH_BAD_OFFSETS; a bad sample's node rows are zeros), and every search
+ * stays inside the sample's entries. n_samples*n_entities, n_envs*n_entities
+ * and n_edges must be below 2^31. Both are stateless and asynchronous on
+ * `stream`; arguments are checked on the host first (GSM_EINVAL). */
+#define GSM_BATCH_BAD_INDEX 1    /* a slot or env index out of range            */
+#define GSM_BATCH_TRUNCATED 2    /* a sample's slot overflowed edge_capacity    */
+#define GSM_BATCH_BAD_OFFSETS 4  /* offsets not 0 <= start <= end / scan mismatch */
+#define GSM_BATCH_OUT_OF_ENV 8   /* an entry's id outside its env               */
+#define GSM_BATCH_ASYMMETRIC 16  /* an entry's reverse entry is missing         */
+int gsm_graph_batch_ptr(const int64_t *edge_ptr, int64_t n_slots, int64_t n_envs, int64_t edge_capacity,
+                        const int64_t *t_idx, const int64_t *b_idx, int64_t n_samples, int64_t *sample_ptr,
+                        int32_t *status, void *stream);
+int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, const float *edge_attr,
+                           const int64_t *edge_ptr, int64_t n_slots, int64_t n_envs, int32_t n_entities,
+                           int64_t edge_capacity, const int64_t *t_idx, const int64_t *b_idx,
+                           const int64_t *sample_ptr, int64_t n_samples, int64_t n_edges, float *node_feat_out,
+                           int64_t *row_ptr, int32_t *col, float *edge_attr_out, int32_t *t_edge,
+                           int32_t *status, void *stream);
+
+/* GAE returns of a stored episode of T = n_steps actions in one launch, with
+ * BN = [n_envs][n_agents]: reward f32 [T]BN (entry t: the reward of action t),
+ * value f32 [T+1]BN, done uint8 [T+1][n_envs] (slot t+1: action t ended the
+ * episode), ret f32 [T]BN. One thread per (env, agent) walks t = T-1 down to
+ * 0, each line one correctly rounded fp32 operation at a time:
+ *   m = 1 - done[t+1];  delta = (r[t] + (gamma * v[t+1]) * m) - v[t]
+ *   gae = delta + (gamma_lambda * m) * gae;  ret[t] = gae + v[t]
+ * gamma_lambda = the double product gamma * lambda rounded once to fp32 (the
+ * caller forms it). Stateless; asynchronous on `stream`. */
+int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
+            int32_t n_agents, float gamma, float gamma_lambda, float *ret, void *stream);
+
 /* Episode frames (replaces the pyglet viewer of
  * multiagent/rendering.py, SOURCES.txt:18, used by scripts/render_mpe.py,
  * SOURCES.txt:30, for the demo/ GIFs, readme.md:64). Draws env env_ids[f]
