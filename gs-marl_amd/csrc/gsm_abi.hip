@@ -1578,6 +1578,43 @@ int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, co
     return GSM_OK;
 }
 
+int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                 int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                 const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels, float scale,
+                 int32_t flags, int32_t n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status,
+                 void *stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
+        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (n_entities < 1 || n_entities > GSM_CONV_MAX_ENTITIES)
+        return fail(nullptr, GSM_EINVAL, "n_entities must be in [1, 288]");
+    if (n_envs < 0 || n_envs >= lim || n_envs * n_entities >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_envs >= 0 and n_envs*n_entities < 2^31");
+    if (n_rows_out < 1 || n_rows_out > n_entities)
+        return fail(nullptr, GSM_EINVAL, "n_rows_out must be in [1, n_entities]");
+    if (edge_limit < 0 || edge_limit >= lim) return fail(nullptr, GSM_EINVAL, "edge_limit must be in [0, 2^31)");
+    if (edge_row_stride < edge_limit) return fail(nullptr, GSM_EINVAL, "edge_row_stride must be >= edge_limit");
+    if (flags & ~GSM_CONV_SKIP) return fail(nullptr, GSM_EINVAL, "unknown flags");
+    if (!status) return fail(nullptr, GSM_EINVAL, "status is NULL");
+    hipStream_t s = as_stream(stream);
+    if (n_envs == 0) {
+        if (row_ptr_out) {
+            const hipError_t e = hipMemsetAsync(row_ptr_out, 0, sizeof(int64_t), s);
+            if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv memset");
+        }
+        return GSM_OK;
+    }
+    if (!node_feat || !edge_ptr || !w || !out) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    if (edge_limit > 0 && (!edge_index || (w_e && !edge_attr)))
+        return fail(nullptr, GSM_EINVAL, "edge_index or edge_attr is NULL");
+    if ((uintptr_t)w % 16) return fail(nullptr, GSM_EINVAL, "w must be 16-byte aligned");
+    const hipError_t e = gsm::launch_env_conv(node_feat, edge_ptr, edge_index, edge_row_stride, edge_attr, edge_limit,
+                                              w, w_e, n_envs, n_entities, heads * channels, channels, scale,
+                                              (flags & GSM_CONV_SKIP) != 0, n_rows_out, out, row_ptr_out, status, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv launch");
+    return GSM_OK;
+}
+
 int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
             int32_t n_agents, float gamma, float gamma_lambda, float *ret, void *stream) {
     const int64_t lim = (int64_t)1 << 31;

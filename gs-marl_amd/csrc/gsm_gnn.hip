@@ -4,7 +4,9 @@
 // 2.3.1 requirements.txt:119 — the InforMARL lineage uses PyG TransformerConv).
 //
 // The dense projections (q = W_q x, k = W_k x, v = W_v x, skip = W_r x) are
-// GEMMs and stay on hipBLASLt (torch.matmul). This kernel is the part that is
+// GEMMs and stay on hipBLASLt (torch.matmul), except for the first layer on an
+// env-form graph, whose K = 7 projections gsm_env_conv (below) forms on chip
+// together with the attention. This kernel is the part that is
 // a gather / segmented softmax / scatter over the graph, for target node i with
 // source neighbours j (CSR rows: row_ptr / col), per head h:
 //
@@ -738,6 +740,353 @@ hipError_t launch_gae(const float *reward, const float *value, const uint8_t *do
     (void)hipGetLastError();
     gsm_gae_kernel<<<(unsigned)((BN + 255) / 256), 256, 0, s>>>(reward, value, done, T, BN, N, gamma,
                                                                 gamma_lambda, ret);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Fused first layer on env-form graphs (gsm_env_conv): the four K = 7
+// projections and the attention of one TransformerConv(7, C, heads) layer in
+// one launch, straight from node_feat [B][E][7] and the env's packed edge list.
+// Edges never leave their env and an env's entries are contiguous and sorted
+// by row, so a workgroup keeps whole envs on chip (max(1, 64 / E) of them, so
+// that small envs fill the block's node slots):
+//
+//   ranges    thread g < envs: edge_ptr[b], edge_ptr[b+1] checked against
+//             0 <= start <= end <= edge_limit (else the env counts 0 entries)
+//   rows      the envs' 7-float rows -> LDS, 8 floats a row (two 16-byte reads)
+//   entries   one coalesced pass over the envs' row and col ids: every id
+//             checked against [bE, (b+1)E) and every row against its
+//             predecessor; the first entry of a run of equal rows writes the
+//             row starts of the rows it opens (row_start[r] = position, for r
+//             in (previous row, row]), so the per-node offsets need neither a
+//             bincount nor a search. An env that fails a check is edgeless.
+//   table     k_j, v_j of every node once per env -> LDS (table form), when
+//             rows + offsets + 2 * nodes * HC floats fit 64 KiB (two or more
+//             workgroups a CU); else k_j, v_j are recomputed from the source's
+//             row for every entry (recompute form: E = 288 with HC >= 24)
+//   walk      kLP lanes per output row, kVec channels per lane, the online
+//             softmax of gsm_attn_aggregate over the row's entries in ascending
+//             order; q_i and skip_i formed from the row in LDS; the sources'
+//             k_j, v_j come from the LDS table (or the LDS rows), the column
+//             ids and distances from global memory one entry ahead
+//
+// A projection is acc = bias, then acc = acc + W[c][f] * x[f] for f = 0..6,
+// one fp32 operation per step (no contraction), in both forms, so the two
+// forms agree bit for bit; no atomics on floats: the output is reproducible.
+
+constexpr int kConvThreads = 256;
+constexpr int kConvLdsMax = 64 * 1024;
+
+struct ConvParams {
+    const float *node_feat;
+    const int64_t *edge_ptr;
+    const int32_t *erow, *ecol;
+    const float *edge_attr;
+    int64_t edge_limit;
+    const float *w, *w_e;
+    int B, E, epb, HC, C, skip, n_rows_out;
+    float scale;
+    float *out;
+    int64_t *row_ptr_out;
+    int32_t *status;
+};
+
+// byte offsets of the workgroup's LDS regions
+struct ConvLds {
+    int xs, est, ecnt, ebad, rs, tab, total;
+};
+__host__ __device__ inline ConvLds conv_lds(int epb, int E, int HC, bool table) {
+    ConvLds l;
+    const int n = epb * E;
+    l.xs = 0;                                   // f32 [n][8]
+    l.est = l.xs + n * 32;                      // int64 [epb] checked start
+    l.ecnt = l.est + epb * 8;                   // int [epb] checked entry count
+    l.ebad = l.ecnt + epb * 4;                  // int [epb] an entry failed its check
+    l.rs = l.ebad + epb * 4;                    // int [epb][E+1] row starts inside the env
+    l.tab = (l.rs + epb * (E + 1) * 4 + 15) & ~15;   // f32 [2][n][HC] k, v
+    l.total = l.tab + (table ? 2 * n * HC * 4 : 0);
+    return l;
+}
+
+// rows c .. c+kVec-1 of weight block blk: [HC][8] = 7 weights and the bias
+template <int kVec>
+__device__ __forceinline__ void conv_load_w(const float *__restrict__ w, int blk, int HC, int ch, bool on,
+                                            float (&r)[kVec][8]) {
+#pragma unroll
+    for (int i = 0; i < kVec; ++i) {
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+        if (on) {
+            const float4 *src = (const float4 *)(w + ((int64_t)blk * HC + ch + i) * 8);
+            a = src[0];
+            b = src[1];
+        }
+        r[i][0] = a.x, r[i][1] = a.y, r[i][2] = a.z, r[i][3] = a.w;
+        r[i][4] = b.x, r[i][5] = b.y, r[i][6] = b.z, r[i][7] = b.w;
+    }
+}
+
+template <int kVec>
+__device__ __forceinline__ typename VecT<kVec>::T conv_project(const float (&wr)[kVec][8], const float4 &x0,
+                                                               const float4 &x1) {
+    typename VecT<kVec>::T r;
+#pragma unroll
+    for (int i = 0; i < kVec; ++i) {
+        float acc = wr[i][7];
+        acc = acc + wr[i][0] * x0.x;
+        acc = acc + wr[i][1] * x0.y;
+        acc = acc + wr[i][2] * x0.z;
+        acc = acc + wr[i][3] * x0.w;
+        acc = acc + wr[i][4] * x1.x;
+        acc = acc + wr[i][5] * x1.y;
+        acc = acc + wr[i][6] * x1.z;
+        VecT<kVec>::set(r, i, acc);
+    }
+    return r;
+}
+
+// the table form is held to 128 VGPRs (four waves a SIMD); the recompute form
+// keeps all four weight blocks in registers at two
+template <int kLP, int kVec, bool kTable>
+__global__ __launch_bounds__(kConvThreads, kTable ? 4 : 2) void gsm_env_conv_kernel(const ConvParams p) {
+    using V = VecT<kVec>;
+    using T = typename V::T;
+    constexpr int kNPP = kConvThreads / kLP;                 // output rows per pass of the block
+    extern __shared__ float4 conv_smem[];
+    char *sm = (char *)conv_smem;
+    const int E = p.E, HC = p.HC;
+    const ConvLds L = conv_lds(p.epb, E, HC, kTable);
+    float *xs = (float *)(sm + L.xs);
+    int64_t *est = (int64_t *)(sm + L.est);
+    int *ecnt = (int *)(sm + L.ecnt), *ebad = (int *)(sm + L.ebad), *rs = (int *)(sm + L.rs);
+    float *ktab = (float *)(sm + L.tab), *vtab = ktab + p.epb * E * HC;
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * p.epb;                       // grid = ceil(B / epb): b0 < B
+    const int ne = min(p.epb, p.B - b0), n_loc = ne * E;
+    int bits = 0;
+
+    // ranges: every offset checked before it bounds a loop or forms an address
+    if (tid < ne) {
+        const int64_t a = p.edge_ptr[b0 + tid], e = p.edge_ptr[b0 + tid + 1];
+        int cnt = 0;
+        if (e > p.edge_limit) bits |= GSM_BATCH_TRUNCATED;
+        else if (a < 0 || e < a) bits |= GSM_BATCH_BAD_OFFSETS;
+        else cnt = (int)(e - a);                             // <= edge_limit < 2^31
+        est[tid] = a < 0 ? 0 : (a > p.edge_limit ? p.edge_limit : a);
+        ecnt[tid] = cnt;
+        ebad[tid] = 0;
+    }
+    // rows: n_loc * 7 contiguous floats
+    {
+        const float *src = p.node_feat + (int64_t)b0 * E * 7;
+        for (int x = tid; x < n_loc * 7; x += kConvThreads) {
+            const int nd = x / 7;
+            xs[nd * 8 + (x - nd * 7)] = src[x];
+        }
+    }
+    __syncthreads();
+
+    // entries: ids and order checked, row starts marked
+    for (int g = 0; g < ne; ++g) {
+        const int cnt = ecnt[g];
+        int *r = rs + g * (E + 1);
+        if (cnt == 0) {
+            for (int x = tid; x <= E; x += kConvThreads) r[x] = 0;
+            continue;
+        }
+        const int64_t s = est[g];
+        const uint32_t bE = (uint32_t)(b0 + g) * (uint32_t)E;   // B * E < 2^31 (host-checked)
+        for (int q = tid; q < cnt; q += kConvThreads) {
+            const uint32_t ri = (uint32_t)p.erow[s + q] - bE, ci = (uint32_t)p.ecol[s + q] - bE;
+            const uint32_t pr = q ? (uint32_t)p.erow[s + q - 1] - bE : 0u;
+            // pr <= ri < E: both rows inside the env and ascending
+            if (!(ri < (uint32_t)E && ci < (uint32_t)E && pr <= ri)) {
+                ebad[g] = 1;
+                continue;
+            }
+            for (int x = q ? (int)pr + 1 : 0; x <= (int)ri; ++x) r[x] = q;
+            if (q == cnt - 1)
+                for (int x = (int)ri + 1; x <= E; ++x) r[x] = cnt;
+        }
+    }
+    __syncthreads();
+    if (tid < ne && ebad[tid]) bits |= GSM_BATCH_OUT_OF_ENV;
+    if (bits) atomicOr(p.status, bits);
+
+    // the per-node offsets env_csr would give (a failed env repeats its start)
+    if (p.row_ptr_out) {
+        for (int x = tid; x < n_loc; x += kConvThreads) {
+            const int g = x / E;
+            p.row_ptr_out[(int64_t)b0 * E + x] = est[g] + (ebad[g] ? 0 : rs[g * (E + 1) + (x - g * E)]);
+        }
+        if (b0 + ne == p.B && tid == 0)
+            p.row_ptr_out[(int64_t)p.B * E] = est[ne - 1] + (ebad[ne - 1] ? 0 : ecnt[ne - 1]);
+    }
+
+    const int slot = tid / kLP, ch = (tid % kLP) * kVec;
+    const bool chon = ch < HC;
+    if constexpr (kTable) {
+        float wk[kVec][8], wv[kVec][8];
+        conv_load_w<kVec>(p.w, 1, HC, ch, chon, wk);
+        conv_load_w<kVec>(p.w, 2, HC, ch, chon, wv);
+        if (chon)
+            for (int x = slot; x < n_loc; x += kNPP) {
+                const float4 x0 = *(const float4 *)(xs + x * 8), x1 = *(const float4 *)(xs + x * 8 + 4);
+                *(T *)(ktab + x * HC + ch) = conv_project<kVec>(wk, x0, x1);
+                *(T *)(vtab + x * HC + ch) = conv_project<kVec>(wv, x0, x1);
+            }
+        __syncthreads();
+    }
+
+    const int lanes_per_head = p.C / kVec;                   // power of two
+    float wq[kVec][8], ws[kVec][8], wk[kVec][8], wv[kVec][8];
+    conv_load_w<kVec>(p.w, 0, HC, ch, chon, wq);
+    conv_load_w<kVec>(p.w, 3, HC, ch, chon && p.skip, ws);
+    if constexpr (!kTable) {
+        conv_load_w<kVec>(p.w, 1, HC, ch, chon, wk);
+        conv_load_w<kVec>(p.w, 2, HC, ch, chon, wv);
+    }
+    T we;
+    for (int i = 0; i < kVec; ++i) V::set(we, i, 0.0f);
+    if (chon && p.w_e) we = *(const T *)(p.w_e + ch);
+    const int R = p.n_rows_out, n_walk = ne * R;
+    for (int base = 0; base < n_walk; base += kNPP) {        // block-uniform trip count
+        const int idx = base + slot;
+        const bool have = idx < n_walk, live = have && chon;
+        const int id = have ? idx : 0;
+        const int g = id / R, i = id - g * R, gE = g * E;
+        const float4 x0 = *(const float4 *)(xs + (gE + i) * 8), x1 = *(const float4 *)(xs + (gE + i) * 8 + 4);
+        const T qi = conv_project<kVec>(wq, x0, x1);
+        const T sk = conv_project<kVec>(ws, x0, x1);
+        const bool good = have && !ebad[g];
+        const int r0 = good ? rs[g * (E + 1) + i] : 0;
+        const int deg = good ? rs[g * (E + 1) + i + 1] - r0 : 0;
+        const int32_t *colp = p.ecol + est[g] + r0;
+        const float *attrp = p.edge_attr + est[g] + r0;
+        const uint32_t bE = (uint32_t)(b0 + g) * (uint32_t)E;
+        int wdeg = deg;                                      // the wave runs its longest row
+#pragma unroll
+        for (int o = kLP; o < kWave; o <<= 1) wdeg = max(wdeg, __shfl_xor(wdeg, o));
+        T acc;
+        for (int c = 0; c < kVec; ++c) V::set(acc, c, 0.0f);
+        float mx = -__builtin_inff(), den = 0.0f;
+        // next entry's source and distance fetched one iteration ahead
+        int32_t jn = (live && deg > 0) ? colp[0] : 0;
+        float wn = (live && deg > 0 && p.w_e) ? attrp[0] : 0.0f;
+        for (int t = 0; t < wdeg; ++t) {
+            const bool on = live && t < deg;
+            const int jl = min(max((int)((uint32_t)jn - bE), 0), E - 1);   // checked above; clamped again
+            const float w = wn;
+            if (live && t + 1 < deg) {
+                jn = colp[t + 1];
+                if (p.w_e) wn = attrp[t + 1];
+            }
+            T kj, vj;
+            for (int c = 0; c < kVec; ++c) {
+                V::set(kj, c, 0.0f);
+                V::set(vj, c, 0.0f);
+            }
+            if (on) {
+                if constexpr (kTable) {
+                    kj = *(const T *)(ktab + (gE + jl) * HC + ch);
+                    vj = *(const T *)(vtab + (gE + jl) * HC + ch);
+                } else {
+                    const float4 y0 = *(const float4 *)(xs + (gE + jl) * 8),
+                                 y1 = *(const float4 *)(xs + (gE + jl) * 8 + 4);
+                    kj = conv_project<kVec>(wk, y0, y1);
+                    vj = conv_project<kVec>(wv, y0, y1);
+                }
+            }
+            float sc = 0.0f;
+#pragma unroll
+            for (int c = 0; c < kVec; ++c) sc += V::get(qi, c) * (V::get(kj, c) + w * V::get(we, c));
+#pragma unroll
+            for (int o = 1; o < kLP; o <<= 1)
+                if (o < lanes_per_head) sc += __shfl_xor(sc, o);   // sum over the head's lanes
+            sc *= p.scale;
+            if (on) {
+                const float m2 = fmaxf(mx, sc);
+                const float a = __expf(mx - m2), b = __expf(sc - m2);
+                den = den * a + b;
+#pragma unroll
+                for (int c = 0; c < kVec; ++c)
+                    V::set(acc, c, V::get(acc, c) * a + b * (V::get(vj, c) + w * V::get(we, c)));
+                mx = m2;
+            }
+        }
+        if (live) {
+            const float inv = den > 0.0f ? 1.0f / den : 0.0f;
+            T r;
+#pragma unroll
+            for (int c = 0; c < kVec; ++c)
+                V::set(r, c, V::get(acc, c) * inv + (p.skip ? V::get(sk, c) : 0.0f));
+            *(T *)(p.out + ((int64_t)(b0 + g) * R + i) * HC + ch) = r;
+        }
+    }
+}
+
+hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                           int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                           const float *w_e, int64_t B, int E, int HC, int C, float scale, bool skip,
+                           int n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status, hipStream_t s) {
+    // four channels per lane when every head spans whole lanes and the rows are 16-byte aligned
+    const bool vec4 = C % 4 == 0 && HC % 4 == 0 &&
+                      ((uintptr_t)out | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
+    const int vec = vec4 ? 4 : 1;
+    int lp = 1;
+    while (lp * vec < HC) lp <<= 1;
+    if (lp > kWave) return hipErrorInvalidValue;
+    ConvParams p;
+    p.node_feat = node_feat;
+    p.edge_ptr = edge_ptr;
+    p.erow = edge_index;
+    p.ecol = edge_index ? edge_index + edge_row_stride : nullptr;
+    p.edge_attr = edge_attr;
+    p.edge_limit = edge_limit;
+    p.w = w;
+    p.w_e = w_e;
+    p.B = (int)B;
+    p.E = E;
+    p.epb = E >= 64 ? 1 : 64 / E;
+    p.HC = HC;
+    p.C = C;
+    p.skip = skip;
+    p.n_rows_out = n_rows_out;
+    p.scale = scale;
+    p.out = out;
+    p.row_ptr_out = row_ptr_out;
+    p.status = status;
+    const bool table = conv_lds(p.epb, E, HC, true).total <= kConvLdsMax;
+    const size_t lds = (size_t)conv_lds(p.epb, E, HC, table).total;
+    if (lds > (size_t)kConvLdsMax) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((B + p.epb - 1) / p.epb);
+    (void)hipGetLastError();
+#define GSM_CONV(LP, VEC)                                                                     \
+    do {                                                                                      \
+        if (table) gsm_env_conv_kernel<LP, VEC, true><<<blocks, kConvThreads, lds, s>>>(p);   \
+        else gsm_env_conv_kernel<LP, VEC, false><<<blocks, kConvThreads, lds, s>>>(p);        \
+    } while (0)
+    if (vec4) {
+        switch (lp) {
+            case 1: GSM_CONV(1, 4); break;
+            case 2: GSM_CONV(2, 4); break;
+            case 4: GSM_CONV(4, 4); break;
+            case 8: GSM_CONV(8, 4); break;
+            case 16: GSM_CONV(16, 4); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (lp) {
+            case 1: GSM_CONV(1, 1); break;
+            case 2: GSM_CONV(2, 1); break;
+            case 4: GSM_CONV(4, 1); break;
+            case 8: GSM_CONV(8, 1); break;
+            case 16: GSM_CONV(16, 1); break;
+            case 32: GSM_CONV(32, 1); break;
+            case 64: GSM_CONV(64, 1); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
+#undef GSM_CONV
     return hipGetLastError();
 }
 

@@ -286,6 +286,11 @@ hipError_t launch_graph_batch_gather(const float *node_feat, const int32_t *edge
                                      int64_t K, int64_t n_edges, float *node_feat_out, int64_t *row_ptr,
                                      int32_t *col, float *attr_out, int32_t *t_edge, int32_t *status,
                                      hipStream_t s);
+// fused first layer on env-form graphs (gsm_gnn.hip)
+hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                           int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                           const float *w_e, int64_t B, int E, int HC, int C, float scale, bool skip,
+                           int n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status, hipStream_t s);
 hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
                       float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,

@@ -21,6 +21,7 @@ GRAPH_UNFUSED, GRAPH_LAG_ONLY, GRAPH_ROLL = 16, 32, 64
 RENDER_EDGES = 1
 ACT_ONEHOT, ACT_INDEX, ACT_CONT = 0, 1, 2
 BATCH_BAD_INDEX, BATCH_TRUNCATED, BATCH_BAD_OFFSETS, BATCH_OUT_OF_ENV, BATCH_ASYMMETRIC = 1, 2, 4, 8, 16
+CONV_SKIP, CONV_MAX_ENTITIES = 1, 288
 
 
 class GsmConfig(C.Structure):
@@ -107,6 +108,8 @@ SIGNATURES = {
     "gsm_graph_batch_ptr": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
     "gsm_graph_batch_gather": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P,
                                          C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "gsm_env_conv": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gsm_gae": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "gsm_render": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

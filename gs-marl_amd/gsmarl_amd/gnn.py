@@ -22,6 +22,13 @@ restates that layer:
   formulation ``GraphRolloutBuffer.graph_batch_csr``'s gather kernel
   (``gsm_graph_batch_gather``) is written against.
 
+* ``env_conv`` is the whole first layer (``in_channels = 7``: the four
+  projections and the attention) as one HIP launch straight from the env-form
+  graph of ``GpuBatchEnv.step`` / ``GraphRolloutBuffer.slot`` (``gsm_env_conv``):
+  no ``env_csr``, no [n, HC] tensors; ``TransformerConv.forward_env`` takes it on
+  the inference path and ``env_conv_ref`` (plain torch, differentiable)
+  elsewhere.
+
 Graph format: CSR over targets (``row_ptr`` [n+1] int64, ``col`` int32
 sources, ``edge_w`` per CSR entry). The env graphs are symmetric (every radius
 edge and agent<->goal edge is emitted both ways), so the row-major COO the
@@ -285,6 +292,118 @@ def attn_aggregate(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, head
     return out
 
 
+def pack_conv_params(conv):
+    """The projections of a ``TransformerConv`` (``concat=True``) in the layout
+    ``gsm_env_conv`` reads: ``w`` [3 or 4, HC, in_channels+1], the blocks
+    query, key, value and (with ``root_weight``) skip, a row = the weights of
+    the input features then the bias (for ``in_channels = 7`` a 32-byte row);
+    ``w_e`` [HC] = the edge projection, or None with ``edge_dim=None``.
+    Differentiable (a ``cat`` of the parameters)."""
+    if not conv.concat:
+        raise ValueError("pack_conv_params: concat=True layers only")
+    lins = [conv.lin_query, conv.lin_key, conv.lin_value] + ([conv.lin_skip] if conv.lin_skip is not None else [])
+    w = torch.stack([torch.cat([l.weight, l.bias[:, None]], 1) for l in lins]).contiguous()
+    w_e = conv.lin_edge.weight[:, 0].contiguous() if conv.lin_edge is not None else None
+    return w, w_e
+
+
+def _env_graph_total(edge_ptr, edge_index):
+    total = int(edge_ptr[-1])
+    if total > edge_index.shape[1]:
+        raise ValueError(f"the graph's {total} entries run past the {edge_index.shape[1]} stored (a truncated "
+                         "rollout slot); size the buffer with a larger edge capacity")
+    return total
+
+
+def env_conv_ref(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out, skip, row_ptr=False):
+    """``env_conv`` in plain torch on any device and dtype (differentiable):
+    ``env_csr``, the linear maps of ``w``, ``attn_aggregate_ref`` and the row
+    slice. The reference of the kernel and the fallback of ``forward_env``.
+    Returns ``out`` [B, rows_out, HC], or ``(out, row_ptr)``."""
+    B, E, F = node_feat.shape
+    n = B * E
+    if w.shape[0] != (4 if skip else 3) or w.shape[2] != F + 1:
+        raise ValueError("w: [4 if skip else 3, heads*channels, in_channels+1]")
+    total = _env_graph_total(edge_ptr, edge_index)
+    ei = edge_index[:, :total]
+    ptr = env_csr(ei, n)
+    x = node_feat.reshape(n, F)
+    q, k, v = (x @ w[i, :, :F].t() + w[i, :, F] for i in range(3))
+    sk = x @ w[3, :, :F].t() + w[3, :, F] if skip else None
+    ew = edge_attr.reshape(-1)[:total] if w_e is not None else None
+    out = attn_aggregate_ref(q, k, v, ptr, ei[1], ew, w_e, sk, heads)
+    out = out.view(B, E, -1)[:, :rows_out]
+    return (out, ptr) if row_ptr else out
+
+
+def env_conv(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out, skip, row_ptr=False, check=True):
+    """One TransformerConv layer (in_channels 7, edge_dim 1 or None, concat) on
+    an env-form graph in one HIP launch (gsm_env_conv in include/gsm.h; no
+    autograd). ``node_feat`` f32 [B, E, 7]; ``edge_ptr`` int64 [B+1];
+    ``edge_index`` int32 [2, cap] or its ``[:, :total]`` view (the row stride
+    is taken from the tensor, the entry bound is ``shape[1]``); ``edge_attr``
+    f32 with at least that many entries; ``w``, ``w_e`` from
+    ``pack_conv_params``; ``rows_out``: E for every row, N for the agents'.
+    Returns ``out`` [B, rows_out, HC], then ``row_ptr`` int64 [B*E+1] (the
+    offsets ``env_csr`` gives) when asked for. With ``check`` one read of the
+    kernel's status raises ValueError for an env whose entries run past the
+    bound (a truncated rollout slot) and RuntimeError for corrupt offsets or
+    ids; without it the status (device int32 [1], GSM_BATCH_* bits) is
+    returned last and such envs are edgeless."""
+    dev = node_feat.device
+    if dev.type != "cuda":
+        raise _lib.GsmError("env_conv needs a ROCm GPU; use env_conv_ref on the CPU")
+    if node_feat.dim() != 3 or node_feat.shape[2] != 7:
+        raise ValueError("node_feat: [B, E, 7]")
+    B, E, _ = node_feat.shape
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index: [2, cap]")
+    limit = int(edge_index.shape[1])
+    edge_attr = edge_attr.reshape(-1) if edge_attr.dim() != 1 else edge_attr
+    for name, t, dt, contig in (("node_feat", node_feat, torch.float32, True), ("edge_ptr", edge_ptr, torch.int64, True),
+                                ("edge_index", edge_index, torch.int32, False),
+                                ("edge_attr", edge_attr, torch.float32, True), ("w", w, torch.float32, True)):
+        if t.dtype != dt or t.device != dev or (contig and not t.is_contiguous()):
+            raise ValueError(f"{name}: need a {'contiguous ' if contig else ''}{dt} tensor on {dev}")
+    if limit and edge_index.stride(1) != 1:
+        raise ValueError("edge_index: rows must be contiguous")
+    if edge_ptr.numel() != B + 1 or edge_attr.numel() < limit:
+        raise ValueError("edge_ptr: [B+1]; edge_attr: one distance per edge_index column")
+    if w.dim() != 3 or w.shape[0] != (4 if skip else 3) or w.shape[2] != 8 or w.shape[1] % heads:
+        raise ValueError("w: [4 if skip else 3, heads*channels, 8]")
+    HC = int(w.shape[1])
+    if w_e is not None:
+        w_e = w_e.contiguous()
+        if w_e.dtype != torch.float32 or w_e.device != dev or w_e.numel() != HC:
+            raise ValueError(f"w_e: float32 [heads*channels] on {dev}")
+    Cc = HC // heads
+    lib = _lib.load()
+    out = torch.empty(B, int(rows_out), HC, dtype=torch.float32, device=dev)
+    ptr = torch.empty(B * E + 1, dtype=torch.int64, device=dev) if row_ptr else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stride = int(edge_index.stride(0)) if limit else 0
+    rc = lib.gsm_env_conv(_ptr(node_feat) if B else None, _ptr(edge_ptr), _ptr(edge_index) if limit else None, stride,
+                          _ptr(edge_attr) if limit else None, limit, _ptr(w), _ptr(w_e), int(B), int(E), int(heads),
+                          int(Cc), 1.0 / math.sqrt(Cc), _lib.CONV_SKIP if skip else 0, int(rows_out), _ptr(out),
+                          _ptr(ptr), _ptr(status), stream)
+    _lib.check(lib, rc, None, "gsm_env_conv")
+    res = (out,) + ((ptr,) if row_ptr else ())
+    if check:
+        st = int(status.item())
+        if st & _lib.BATCH_TRUNCATED:
+            raise ValueError(f"env_conv: an env's entries run past the {limit} stored (a truncated rollout slot); "
+                             "size the buffer with a larger edge capacity")
+        if st:
+            what = [m for bit, m in ((_lib.BATCH_BAD_OFFSETS, "an env's edge offsets are not 0 <= start <= end"),
+                                     (_lib.BATCH_OUT_OF_ENV, "an entry's node id lies outside its env or its rows "
+                                                             "do not ascend")) if st & bit]
+            raise RuntimeError(f"env_conv: the graph is invalid (status {st}): " + "; ".join(what))
+    else:
+        res = res + (status,)
+    return res[0] if len(res) == 1 else res
+
+
 class TransformerConv(torch.nn.Module):
     """``TransformerConv(in_channels, out_channels, heads, concat, edge_dim=1,
     root_weight=True)`` in the torch-geometric parameterisation, with the
@@ -292,7 +411,9 @@ class TransformerConv(torch.nn.Module):
     ``kernel_backward=True`` (and ``use_kernel``, on the GPU) the training path
     takes the HIP forward and backward kernels (``attn_aggregate_autograd``)
     too; ``forward(..., transpose=csr_transpose(row_ptr, col))`` reuses the
-    transposed graph across calls. The default keeps the torch formulation."""
+    transposed graph across calls. The default keeps the torch formulation.
+    ``forward_env`` is the layer on an env-form graph (what the env returns, or
+    a rollout-buffer slot), fused into one launch where ``env_conv`` applies."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
                  edge_dim: Optional[int] = 1, root_weight: bool = True, use_kernel: bool = True,
@@ -330,3 +451,61 @@ class TransformerConv(torch.nn.Module):
             if self.lin_skip is not None:
                 out = out + self.lin_skip(x)
         return out
+
+    def _env_kernel_ok(self, node_feat, edge_attr):
+        if not (self.use_kernel and self.concat and node_feat.is_cuda and node_feat.dtype == torch.float32):
+            return False
+        if self.lin_query.in_features != 7 or (self.lin_edge is not None and self.lin_edge.in_features != 1):
+            return False
+        if torch.is_grad_enabled() and (node_feat.requires_grad or edge_attr.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
+            return False
+        B, E, _ = node_feat.shape
+        Cc, HC = self.out_channels, self.heads * self.out_channels
+        return Cc & (Cc - 1) == 0 and HC <= 64 and 1 <= E <= _lib.CONV_MAX_ENTITIES and B * E < 2 ** 31
+
+    def _packed(self):
+        """``pack_conv_params`` of the current parameter values, packed again
+        only after a parameter changed (inference path, no gradient)."""
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if getattr(self, "_pack_key", None) != key:
+            with torch.no_grad():
+                self._pack = tuple(t.float() if t is not None else None for t in pack_conv_params(self))
+            self._pack_key = key
+        return self._pack
+
+    def forward_env(self, graph: dict, rows: str = "all", n_agents: Optional[int] = None, row_ptr: bool = False):
+        """The layer on an env-form graph: any dict with ``node_feat`` [B, E,
+        F], ``edge_ptr`` [B+1], ``edge_index`` [2, cap or total] (global ids) and
+        ``edge_attr``: what ``GpuBatchEnv.step`` / ``reset`` / ``observe`` return
+        (either ``sync_edges``) or ``GraphRolloutBuffer.slot(t)``. Returns [B,
+        rows, HC]: every row (``rows="all"``) or the first ``n_agents`` of each
+        env (``rows="agents"``); with ``row_ptr`` also the per-node offsets of
+        ``env_csr``, for a further layer on ``forward``. One HIP launch
+        (``env_conv``) when the tensors are on the GPU, no gradient is wanted,
+        ``use_kernel``, ``concat``, 7 input features, edge_dim 1 or None and the
+        kernel's shape limits hold; the differentiable torch formulation
+        (``env_conv_ref``) otherwise."""
+        nf, ei, ea = graph["node_feat"], graph["edge_index"], graph["edge_attr"]
+        B, E, F = nf.shape
+        if rows == "all":
+            R = E
+        elif rows == "agents":
+            if n_agents is None or not 1 <= n_agents <= E:
+                raise ValueError('rows="agents" needs n_agents in [1, E]')
+            R = int(n_agents)
+        else:
+            raise ValueError('rows: "all" or "agents"')
+        if self._env_kernel_ok(nf, ea):
+            w, w_e = self._packed()
+            return env_conv(nf.contiguous(), graph["edge_ptr"], ei, ea, w, w_e, self.heads, R,
+                            self.lin_skip is not None, row_ptr=row_ptr)
+        if self.concat:
+            w, w_e = pack_conv_params(self)
+            return env_conv_ref(nf, graph["edge_ptr"], ei, ea, w, w_e, self.heads, R, self.lin_skip is not None,
+                                row_ptr=row_ptr)
+        total = _env_graph_total(graph["edge_ptr"], ei)
+        ptr = env_csr(ei[:, :total], B * E)
+        out = self.forward(nf.reshape(B * E, F), ptr, ei[1, :total], ea.reshape(-1)[:total, None])
+        out = out.view(B, E, -1)[:, :R]
+        return (out, ptr) if row_ptr else out

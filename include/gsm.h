@@ -441,6 +441,45 @@ int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, co
                            int64_t *row_ptr, int32_t *col, float *edge_attr_out, int32_t *t_edge,
                            int32_t *status, void *stream);
 
+/* One TransformerConv layer (in_channels = 7, edge_dim = 1, concat) straight
+ * from the env-form graph of a live env or of one rollout-buffer slot: the
+ * projections q, k, v (and skip) and the attention of gsm_attn_aggregate in
+ * one launch, an env kept on chip. node_feat f32 [n_envs][n_entities][7];
+ * edge_ptr int64 [n_envs+1]; edge_index int32, row 0 (targets) at edge_index
+ * and row 1 (sources) at edge_index + edge_row_stride, global ids
+ * b*n_entities + e, an env's entries sorted by (row, col); edge_attr f32;
+ * edge_limit: the valid entries of the edge arrays (the bound capacity, or a
+ * slot's). w f32 [3 or 4][heads*channels][8], 16-byte aligned: the blocks q,
+ * k, v and, with GSM_CONV_SKIP, skip; columns 0-6 of a row the weights of the
+ * 7 features, column 7 the bias. w_e f32 [heads*channels] or NULL (no edge
+ * term). For entry p of env b, i = row - bE, j = col - bE, per head h:
+ *   q_i, k_j, v_j, skip_i: acc = bias; acc = acc + W[c][f] * x[f], f = 0..6,
+ *                          one fp32 operation a step, in that order
+ *   e_ij = edge_attr[p] * w_e[c];  a_ij = softmax_j(scale * <q_i[h], k_j[h] + e_ij>)
+ *   out_i[h] = sum_j a_ij (v_j[h] + e_ij) + skip_i[h]
+ * the row's entries in ascending order, no float atomics (bitwise
+ * reproducible); an empty row gives skip_i, or exactly 0 without skip.
+ * out f32 [n_envs][n_rows_out][heads*channels]: the first n_rows_out rows of
+ * every env (n_entities: all, n_agents: the agents). row_ptr_out int64
+ * [n_envs*n_entities+1] or NULL: the per-node offsets into the edge arrays
+ * (row_ptr of gsm_attn_aggregate for a further layer). Every offset read is
+ * checked before use, into status (device int32 [1], zeroed by the caller):
+ * an env whose range is not 0 <= start <= end sets GSM_BATCH_BAD_OFFSETS, one
+ * whose range runs past edge_limit GSM_BATCH_TRUNCATED, one with a row or col
+ * outside [bE, (b+1)E) or a row below its predecessor's GSM_BATCH_OUT_OF_ENV;
+ * such an env is treated as edgeless (its rows get skip_i or 0, its
+ * row_ptr_out entries repeat its start clamped into [0, edge_limit]). Shape
+ * limits: channels a power of two, heads*channels <= 64, n_entities <= 288,
+ * n_envs*n_entities and edge_limit < 2^31, edge_row_stride >= edge_limit
+ * (GSM_EINVAL). Stateless; asynchronous on `stream`. */
+#define GSM_CONV_SKIP 1
+#define GSM_CONV_MAX_ENTITIES 288
+int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                 int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                 const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels, float scale,
+                 int32_t flags, int32_t n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status,
+                 void *stream);
+
 /* GAE returns of a stored episode of T = n_steps actions in one launch, with
  * BN = [n_envs][n_agents]: reward f32 [T]BN (entry t: the reward of action t),
  * value f32 [T+1]BN, done uint8 [T+1][n_envs] (slot t+1: action t ended the
