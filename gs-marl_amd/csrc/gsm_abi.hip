@@ -74,12 +74,9 @@ struct gsm_handle {
     hipStream_t roll_stream = nullptr;
     bool roll_launched = false;
     hipEvent_t roll_done = nullptr;   // recorded behind every rollout-slot launch
-    uint32_t eager_last_epoch = 0xffffffffu;   // the eager one-launch step's previous epoch
-    uint64_t *eager_csum = nullptr;           // its chunk-sum halves (segmented: inside eager_gran)
+    uint64_t *eager_csum = nullptr;   // the eager one-launch step's chunk-sum halves (inside eager_gran)
     int64_t eager_csum_half = 0;
-    uint32_t eager_launches = 0;
-    uint32_t *eager_epoch = nullptr;  // the segmented one-launch step's device-side epoch (inside eager_gran)
-    bool eager_dev_epoch = true;      // GSM_EAGER_DEV_EPOCH=0 (an A/B knob): host epochs outside captures
+    uint32_t *eager_epoch = nullptr;  // its device-side epoch (inside eager_gran)
     // gsm_step as a one-step rollout launch (step + its edges in one kernel):
     // -1 not yet decided for this config, 0 no (two launches), 1 yes
     int eager_roll = -1;
@@ -448,7 +445,7 @@ uint32_t fresh_epoch(uint32_t &last) {
 // holds from an earlier read can be served stale until the line leaves the
 // L2, and the hand-off then re-polls. Same box, one run each (profiles/
 // r4_gran): C2 3.44 -> 3.16 us per step, H 8.46 -> 8.31, C3 and C4 within
-// noise. GSM_GRAN_MEM = "hip" / "fine" selects hipMalloc / fine-grained (A/B).
+// noise.
 //
 // The used bytes are placed at the END of a whole number of 4 KiB pages
 // (*gran = *base + the slack): an access past the last granule leaves the
@@ -456,14 +453,7 @@ uint32_t fresh_epoch(uint32_t &last) {
 // gran_chk; the checked build tests every address against the end).
 hipError_t gran_malloc(void **base, uint64_t **gran, size_t bytes) {
     const size_t alloc = (bytes + 4095) & ~(size_t)4095;
-    const char *ev = getenv("GSM_GRAN_MEM");
-    hipError_t e;
-    if (ev && !strcmp(ev, "hip"))
-        e = hipMalloc(base, alloc);
-    else if (ev && !strcmp(ev, "fine"))
-        e = hipExtMallocWithFlags(base, alloc, hipDeviceMallocFinegrained);
-    else
-        e = hipExtMallocWithFlags(base, alloc, hipDeviceMallocUncached);
+    const hipError_t e = hipExtMallocWithFlags(base, alloc, hipDeviceMallocUncached);
     if (e != hipSuccess) {
         *base = nullptr;
         *gran = nullptr;
@@ -477,49 +467,38 @@ hipError_t gran_malloc(void **base, uint64_t **gran, size_t bytes) {
 // step, then its edges at the CSR offset of the in-launch prefix) instead of
 // the step kernel + the emit kernel — the same operations, so the same outputs
 // (tests/test_gpu_roll.py), when the grid fits one residency round (decided
-// once per handle). The default for the one-env-per-wave segmented rollout
+// once per handle). It runs for the one-env-per-wave segmented rollout
 // (navigation with 6, 12 or 24 agents: 15.4 vs 16.5 us per step at H, 13.1 vs
-// 15.5 at 12 x 8192; DESIGN.md §4, profiles/r5_ab/eager_forms); the packed
-// small-env and tile rollouts keep the two launches unless
-// GSM_EAGER_ONE_LAUNCH=1 (there the pair was faster: C2 8.7 vs 9.4, C3 27.9
-// vs 29.6 us), and GSM_EAGER_ONE_LAUNCH=0 keeps them everywhere. The ragged
-// path always runs two launches.
+// 15.5 at 12 x 8192; DESIGN.md §4, profiles/r5_ab/eager_forms) unless
+// GSM_EAGER_ONE_LAUNCH=0 asks for the two launches. Every other config runs
+// the two launches: for the packed small-env and tile rollouts they were the
+// faster form (C2 8.7 vs 9.4, C3 27.9 vs 29.6 us), and the ragged path has no
+// one-step form.
 constexpr int kEagerIneligible = 1;
 // Decided once per handle, at gsm_bind (the hand-off granules allocated and
 // zeroed there, so that no step allocates or synchronises): h->eager_roll 1
-// when the config has a rollout kernel whose grid fits one residency round
-// and the one launch is wanted (above), else 0.
+// when the config has an eager rollout kernel whose grid fits one residency
+// round and the two launches were not asked for, else 0.
 int eager_setup(gsm_handle *h) {
     gsm::DevParams p = h->dp;
     p.action_fmt = GSM_ACT_INDEX;   // (every format's kernel has the same LDS and occupancy)
     h->eager_roll = 0;
-    if (p.path == gsm::kPathRagged) return GSM_OK;
-    const bool tile = p.path == gsm::kPathTile;
-    const void *fn = tile ? gsm::roll_tile_kernel_fn(p, false) : gsm::roll_seg_kernel_fn(p, false);
-    if (!fn) return GSM_OK;
-    const int per_blk = tile ? 1 : gsm::roll_seg_envs_per_block(p);
-    const int nb = tile ? gsm::step_grid_blocks(p) : (p.B + per_blk - 1) / per_blk;
-    const size_t lds = tile ? gsm::roll_tile_kernel_lds(p) : gsm::roll_kernel_lds(p);
+    const gsm::RollForm form = gsm::roll_seg_eager_form(p);
+    if (!form.fn) return GSM_OK;
     const char *ev = getenv("GSM_EAGER_ONE_LAUNCH");
-    const bool want = ev && *ev ? atoi(ev) != 0 : !tile && !gsm::roll_packed(p);
-    if (!want) return GSM_OK;
+    if (ev && *ev && atoi(ev) == 0) return GSM_OK;
+    const int nb = (p.B + form.envs - 1) / form.envs;
     const size_t nc = ((size_t)nb + gsm::kPrefixChunk - 1) / gsm::kPrefixChunk;
     if (nc > (size_t)gsm::kWave) return GSM_OK;   // roll_prefix: one chunk sum per lane
-    const char *de = getenv("GSM_EAGER_DEV_EPOCH");
-    h->eager_dev_epoch = !(de && *de && atoi(de) == 0);
     int dev = 0, per_cu = 0, n_cu = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, gsm::roll_block_threads(p), lds);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, form.fn, form.threads, form.lds);
     if (e != hipSuccess) return hip_fail(h, e, "occupancy query (eager rollout)");
     if ((int64_t)per_cu * n_cu < nb) return GSM_OK;
-    // (tile path: aggregates + inclusive prefixes per workgroup;
-    // segmented: aggregates + two halves of chunk sums; packed small envs:
-    // per-wave counts + group sums)
-    const size_t xw = (size_t)nb * gsm::kWavesPerBlock;
-    const size_t words = std::max({2 * (size_t)nb, (size_t)nb + 2 * nc * kCsumStride,
-                                   xw + (xw + gsm::kWave - 1) / gsm::kWave});
-    // then the segmented step's device-side epoch replicas
+    // the workgroups' aggregates and two halves of chunk sums, then the
+    // device-side epoch replicas
+    const size_t words = (size_t)nb + 2 * nc * kCsumStride;
     const size_t epoch_bytes = (size_t)gsm::kEpochReps * gsm::kEpochStride * sizeof(uint32_t);
     const size_t bytes = 16 + words * sizeof(uint64_t) + epoch_bytes;
     if (h->eager_base) {   // (a retried setup)
@@ -556,46 +535,30 @@ int launch_step_roll(gsm_handle *h, gsm::DevParams p, hipStream_t s) {
         const int rc = eager_setup(h);
         if (rc) return rc;
     }
-    if (h->eager_roll == 0 || p.path == gsm::kPathRagged) return kEagerIneligible;
-    const bool tile = p.path == gsm::kPathTile;
-    // one env per wave: the kernel takes its epoch and chunk-sum half from
-    // device memory and advances them itself (gsm_roll_seg_kernel kEager), so
-    // the launch holds no per-launch host state and may be recorded into a
-    // stream capture (torch.cuda.graph around a policy + env.step). The tile
-    // and packed small-env forms take both from the host per launch: on a
-    // capturing stream they give way to the two launches, which hold none.
-    const void *fn = tile ? nullptr : gsm::roll_seg_eager_kernel_fn(p);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (fn && !capturing && !h->eager_dev_epoch) fn = nullptr;
-    const bool dev_epoch = fn != nullptr;
-    if (!dev_epoch) {
-        if (capturing) return kEagerIneligible;
-        fn = tile ? gsm::roll_tile_kernel_fn(p, false) : gsm::roll_seg_kernel_fn(p, false);
-    }
-    if (!fn) return kEagerIneligible;   // (the action format may differ per call: checked every time)
-    const int per_blk = tile ? 1 : gsm::roll_seg_envs_per_block(p);
-    const int nb = tile ? gsm::step_grid_blocks(p) : (p.B + per_blk - 1) / per_blk;
-    const size_t lds = tile ? gsm::roll_tile_kernel_lds(p) : gsm::roll_kernel_lds(p);
+    if (h->eager_roll == 0) return kEagerIneligible;
+    // The kernel takes its epoch and chunk-sum half from device memory and
+    // advances them itself (gsm_roll_seg_kernel kEager), so the launch holds
+    // no per-launch host state and may be recorded into a stream capture
+    // (torch.cuda.graph around a policy + env.step).
+    const gsm::RollForm form = gsm::roll_seg_eager_form(p);   // (the action format may differ per call)
+    if (!form.fn) return kEagerIneligible;
+    const int nb = (p.B + form.envs - 1) / form.envs;
     // the step's outputs: the bound (or redirected) buffers, its edges too
     p.ro = gsm::DevParams::RollOut{p.node_feat, p.reward, p.cost, p.done, p.edge_count, p.edge_ptr, p.edge_index,
                                    p.edge_attr, 0, 0, 0, 0, 0, 0, 0, p.edge_capacity, nullptr, nullptr, p.assign, 0};
-    const int xW = nb * gsm::kWavesPerBlock, xNG = (xW + gsm::kWave - 1) / gsm::kWave;
-    // (one step: no pacing)
-    p.roll = gsm::DevParams::Roll{(const char *)p.actions, 0, 1, 0, 1, xW, xNG, 0, 0, 0, h->eager_gran + 2,
-                                  h->roll_status, dev_epoch ? 0u : fresh_epoch(h->eager_last_epoch)};
-    // (device epoch: the halves in a fixed order, the kernel picks by the
-    // epoch's parity; else this launch's half by the host's launch parity)
-    const int par = dev_epoch ? 0 : (int)(h->eager_launches & 1u);
-    p.roll.csum = h->eager_csum + par * h->eager_csum_half;
-    p.roll.csum_next = h->eager_csum + (1 - par) * h->eager_csum_half;
+    // (one step: no pacing; per-workgroup hand-off: no xW / xNG; the epoch
+    // field unused)
+    p.roll = gsm::DevParams::Roll{(const char *)p.actions, 0, 1, 0, 1, 0, 0, 0, 0, 0, h->eager_gran + 2,
+                                  h->roll_status, 0u};
+    // (the halves in a fixed order: the kernel picks by the epoch's parity)
+    p.roll.csum = h->eager_csum;
+    p.roll.csum_next = h->eager_csum + h->eager_csum_half;
     p.roll.csum_stride = kCsumStride;
     p.roll.gran_end = h->eager_gran_end;
-    p.roll.dev_epoch = dev_epoch ? h->eager_epoch : nullptr;
+    p.roll.dev_epoch = h->eager_epoch;
     void *args[] = {&p};
-    const hipError_t e = hipLaunchKernel(fn, dim3(nb), dim3(gsm::roll_block_threads(p)), args, (unsigned)lds, s);
+    const hipError_t e = hipLaunchKernel(form.fn, dim3(nb), dim3(form.threads), args, (unsigned)form.lds, s);
     if (e != hipSuccess) return hip_fail(h, e, "hipLaunchKernel (one-step rollout)");
-    ++h->eager_launches;   // (only a launched step takes a half: a failed one leaves the order as it was)
     return GSM_OK;
 }
 
@@ -912,13 +875,19 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
         else
             pace_q = std::max(0, atoi(ev));
     }
-    // two envs per wave (gsm_roll_pair_kernel): its grid and LDS differ, so it
-    // is decided here (none of the arguments it depends on changes below)
-    const bool pair = !tile && !ragged && gsm::roll_seg_pair(p, slots, pace_on);
-    const void *roll_fn = tile ? gsm::roll_tile_kernel_fn(p, slots)
-                               : ragged ? gsm::roll_ragged_kernel_fn(p, slots) : gsm::roll_seg_kernel_fn(p, slots, pair);
-    if (!roll_fn && fallback) return kRollIneligible;
-    if (!roll_fn) return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: no fused rollout kernel for this config "
+    // what the launch runs: the kernel, its workgroup, envs per workgroup and
+    // LDS. The segmented path chooses among several kernels by the launch's
+    // arguments (gsm_seg_kernels.hip pick_roll_seg); of those it depends on,
+    // only nf_full changes below (redirect, rollout buffers only), and a
+    // rollout buffer's choice does not depend on it
+    const gsm::RollForm form =
+        tile ? gsm::RollForm{gsm::roll_tile_kernel_fn(p, slots), gsm::block_threads(p), 1,
+                             gsm::roll_tile_kernel_lds(p), false}
+             : ragged ? gsm::RollForm{gsm::roll_ragged_kernel_fn(p, slots), gsm::block_threads(p),
+                                      gsm::kWavesPerBlock, gsm::roll_ragged_kernel_lds(p), true}
+                      : gsm::roll_seg_form(p, slots, pace_on);
+    if (!form.fn && fallback) return kRollIneligible;
+    if (!form.fn) return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: no fused rollout kernel for this config "
                                              "(segmented path with a compiled shape, tile path with the "
                                              "symmetric sweep, or a ragged batch)");
     // step k's outputs at base + k * stride (a rollout buffer's slots) or all
@@ -951,17 +920,14 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     }
     // segmented / ragged rollout: one env per wave whatever the config's G (4 per workgroup), two
     // per wave (8, gsm_roll_pair_kernel), or four small envs per wave (16 per workgroup)
-    const int per_blk = tile ? 1 : ragged ? gsm::kWavesPerBlock : gsm::roll_seg_envs_per_block(p, pair);
-    const int nb = tile ? gsm::step_grid_blocks(p) : (p.B + per_blk - 1) / per_blk;
-    const size_t roll_lds = tile ? gsm::roll_tile_kernel_lds(p)
-                                 : ragged ? gsm::roll_ragged_kernel_lds(p) : gsm::roll_kernel_lds(p, pair);
+    const int nb = (p.B + form.envs - 1) / form.envs;
     // every workgroup resident at once (one residency round; a workgroup only
     // waits on lower-numbered ones, so this is for speed, not for progress)
     int dev = 0, per_cu = 0, n_cu = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     if (e == hipSuccess)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, roll_fn, gsm::roll_block_threads(p), roll_lds);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, form.fn, form.threads, form.lds);
     if (e != hipSuccess) return hip_fail(h, e, "occupancy query");
     if ((int64_t)per_cu * n_cu < nb) {
         if (fallback) return kRollIneligible;
@@ -980,7 +946,7 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     const int xW = nb * gsm::kWavesPerBlock, xNG = (xW + gsm::kWave - 1) / gsm::kWave;
     // per-wave granules (Xfer): ragged and packed small envs; the other
     // segmented shapes and the tile path look back per workgroup
-    const bool per_wave = ragged || (!tile && gsm::roll_packed(p));
+    const bool per_wave = form.per_wave;
     if (per_wave && xNG > 2 * gsm::kWave) {
         if (fallback) return kRollIneligible;
         return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: more than 8192 envs in one rollout launch");
@@ -1123,31 +1089,21 @@ static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_
     p.roll.csum_stride = kCsumStride;   // (csum, pace: set per launch, gsm_graph_launch)
     p.roll.gran_end = (uint64_t *)((char *)sl.gran + gran_alloc);
     p.roll.slab_end = h->slab ? (int32_t *)((char *)h->slab + h->slab_bytes) : nullptr;
-    // the segmented rollout's instantiation for the launch's arguments, final
-    // now (redirected outputs, pacing): the same LDS and no more registers
-    // than the generic one, so the occupancy found above holds
-    if (!tile && !ragged) {
-        if (gsm::roll_seg_pair(p, slots, sl.pace != nullptr) != pair) {
-            drop_slot(sl);
-            return fail(h, GSM_ESTATE, "GSM_GRAPH_ROLL: the rollout kernel's form changed during the capture");
-        }
-        roll_fn = gsm::roll_seg_kernel_fn(p, slots, sl.pace != nullptr);
-    }
     if (e == hipSuccess) {
         what = "rollout kernel node";
         hipKernelNodeParams kp = {};
         void *args[] = {&p};
-        kp.func = const_cast<void *>(roll_fn);
+        kp.func = const_cast<void *>(form.fn);
         kp.gridDim = dim3(nb);
-        kp.blockDim = dim3(gsm::roll_block_threads(p));
-        kp.sharedMemBytes = (unsigned)roll_lds;
+        kp.blockDim = dim3(form.threads);
+        kp.sharedMemBytes = (unsigned)form.lds;
         kp.kernelParams = args;
         kp.extra = nullptr;
         hipGraphNode_t n;
         e = hipGraphAddKernelNode(&n, sl.graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp);
         if (e == hipSuccess) prev = n;
         sl.direct = true;
-        sl.fn = roll_fn;
+        sl.fn = form.fn;
         sl.grid = kp.gridDim;
         sl.block = kp.blockDim;
         sl.lds = kp.sharedMemBytes;

@@ -204,24 +204,32 @@ const void *step_seg_kernel_fn(const DevParams &p);
 const void *lag_step_kernel_fn(const DevParams &p);
 const void *lag_step_seg_kernel_fn(const DevParams &p);
 const void *emit_seg_kernel_fn(const DevParams &p);
-// fused K-step rollout kernel (nullptr where the config has none: G > 1,
-// runtime shapes, other families) and its LDS bytes
-// slots: a rollout buffer's outputs; paced (given with a launch's final
-// arguments): its launches carry pace counters, so the plain instantiation
-// may be chosen where the arguments hold the common configuration
-// (gsm_seg_kernels.hip roll_seg_plain)
-const void *roll_seg_kernel_fn(const DevParams &p, bool slots, bool paced = false);
-// the one-launch eager step (K = 1, device-side epoch; one env per wave shapes)
-const void *roll_seg_eager_kernel_fn(const DevParams &p);
-// whether a launch with these arguments runs the two-envs-per-wave rollout
-// (gsm_roll_pair_kernel: 8 envs per workgroup, its own LDS layout); decided
-// with the launch's final arguments, like the plain instantiation
-bool roll_seg_pair(const DevParams &p, bool slots, bool paced);
-int roll_seg_envs_per_block(const DevParams &p, bool pair = false);
-// the segmented rollout packs four small envs per wave (gsm_roll_pack_kernel):
-// per-wave CSR hand-off granules, as the ragged rollout (Roll::xW / xNG)
-bool roll_packed(const DevParams &p);   // 4 (one env per wave) or 16 (small envs, four per wave)
-size_t roll_kernel_lds(const DevParams &p, bool pair = false);
+// fn = the kernel instantiation for a launch's action format: the last
+// argument names the kernel with kFmt where the format goes, as in
+// GSM_KERNEL_BY_FMT(fn, p.action_fmt, gsm_step_seg_kernel<3, 3, kFmt, false>)
+#define GSM_KERNEL_BY_FMT(fn, fmt, ...)                                                                \
+    switch (fmt) {                                                                                     \
+        case 0: { constexpr int kFmt = 0; fn = reinterpret_cast<const void *>(&__VA_ARGS__); break; }  \
+        case 1: { constexpr int kFmt = 1; fn = reinterpret_cast<const void *>(&__VA_ARGS__); break; }  \
+        default: { constexpr int kFmt = 2; fn = reinterpret_cast<const void *>(&__VA_ARGS__); break; } \
+    }
+// What a segmented rollout launch runs: the kernel and the launch geometry
+// that goes with it, decided together (gsm_seg_kernels.hip pick_roll_seg).
+struct RollForm {
+    const void *fn;   // nullptr: no fused rollout kernel (runtime shapes, other families)
+    int threads;      // per workgroup
+    int envs;         // per workgroup: 4 (one per wave), 8 (two per wave) or 16 (four small envs per wave)
+    size_t lds;       // dynamic LDS bytes
+    bool per_wave;    // per-wave CSR hand-off granules, as the ragged rollout (Roll::xW / xNG); else per workgroup
+};
+// the fused K-step rollout of a graph launch, from the launch's arguments.
+// slots: a rollout buffer's outputs; paced: its launches carry pace counters
+// (where the arguments also hold the common configuration, the plain
+// instantiation or the two-envs-per-wave kernel is chosen)
+RollForm roll_seg_form(const DevParams &p, bool slots, bool paced);
+// the one-launch eager step (K = 1, device-side epoch): the one-env-per-wave
+// shapes only
+RollForm roll_seg_eager_form(const DevParams &p);
 const void *roll_tile_kernel_fn(const DevParams &p, bool slots);   // nullptr unless p.tile_sym
 size_t roll_tile_kernel_lds(const DevParams &p);
 const void *step_ragged_kernel_fn();
@@ -249,10 +257,6 @@ const void *lag_step_ragged_kernel_fn();   // kLag: the previous step's emission
 const void *step_tile_kernel_fn();
 const void *emit_tile_kernel_fn();
 int block_threads(const DevParams &p);
-// threads per workgroup of the config's rollout kernel (the split packed
-// small-env rollout runs 512: four stepping and four emitting waves)
-int roll_block_threads(const DevParams &p);
-bool roll_pack_split(const DevParams &p);
 const void *emit_ragged_kernel_fn();
 // ragged path: per-device constant tables (unit circle, line fractions,
 // half-widths) computed on the host with libm; uploaded once per device.

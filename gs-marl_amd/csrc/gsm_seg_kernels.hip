@@ -1248,7 +1248,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
     // and writes the agents' new positions into buffer (k + 1) % 3, so the
     // positions after step k - 2, which iteration k emits the edges of, are
     // still in the third; goals and obstacles (static within an episode) are
-    // kept in all three. Compile-time layout (roll_kernel_lds): [positions] x 3,
+    // kept in all three. Compile-time layout (roll_lds_wave): [positions] x 3,
     // [staging scratch], [the next step's agent forces], [the row masks of
     // step k - 2], [the scan of their list lengths].
     constexpr int wstride = roll_lds_wave(N, E);
@@ -3334,19 +3334,18 @@ gsm_roll_pack2_kernel(
 // collectives for 24 agents) and action formats; anything else runs the
 // runtime-shape instantiation.
 #define GSM_SEG_SHAPES(X) X(3, 3) X(24, 24)
-// rollout shapes: BASELINE's (3, 24 agents) and the reference's zero-shot
-// navigation sizes 6 and 12 (readme.md:75)
-#define GSM_ROLL_SHAPES(X) X(3, 3) X(6, 6) X(12, 12) X(24, 24)
+// shapes of the one-env-per-wave rollout (gsm_roll_seg_kernel): BASELINE's 24
+// agents and the reference's zero-shot navigation sizes 6 and 12
+// (readme.md:75); BASELINE's 3 agents run the packed kernels below
+#define GSM_ROLL_SHAPES(X) X(6, 6) X(12, 12) X(24, 24)
 
 template <bool LAG>
 static const void *pick_step_seg(const DevParams &p) {
-#define GSM_PICK(n, no)                                                                       \
-    if (p.N == n && p.No == no && p.G == envs_per_wave<n, no>()) {                           \
-        switch (p.action_fmt) {                                                               \
-            case 0: return reinterpret_cast<const void *>(&gsm_step_seg_kernel<n, no, 0, LAG>); \
-            case 1: return reinterpret_cast<const void *>(&gsm_step_seg_kernel<n, no, 1, LAG>); \
-            default: return reinterpret_cast<const void *>(&gsm_step_seg_kernel<n, no, 2, LAG>); \
-        }                                                                                     \
+#define GSM_PICK(n, no)                                                         \
+    if (p.N == n && p.No == no && p.G == envs_per_wave<n, no>()) {              \
+        const void *fn;                                                         \
+        GSM_KERNEL_BY_FMT(fn, p.action_fmt, gsm_step_seg_kernel<n, no, kFmt, LAG>) \
+        return fn;                                                              \
     }
     GSM_SEG_SHAPES(GSM_PICK)
 #undef GSM_PICK
@@ -3357,138 +3356,97 @@ const void *lag_step_seg_kernel_fn(const DevParams &p) { return pick_step_seg<tr
 
 // small shapes run four envs per wave (gsm_roll_pack_kernel)
 #define GSM_PACK_SHAPES(X) X(3, 3)
-bool roll_packed(const DevParams &p) {
-#define GSM_PICK(n, no) if (p.N == n && p.No == no) return true;
-    GSM_PACK_SHAPES(GSM_PICK)
-#undef GSM_PICK
-    return false;
-}
-int roll_seg_envs_per_block(const DevParams &p, bool pair) {
-    return pair ? kPairEnvs : roll_packed(p) ? kWavesPerBlock * kPackG : kWavesPerBlock;
-}
-// the packed small-env rollout with its emission on waves of its own
-// (gsm_roll_pack2_kernel: 512-thread workgroups, two per CU at most, so up to
-// 8192 envs in one residency round; larger batches keep gsm_roll_pack_kernel;
-// GSM_PACK_SPLIT=0 keeps it everywhere, an A/B knob)
-bool roll_pack_split(const DevParams &p) {
-    static const bool on = [] {
-        const char *e = getenv("GSM_PACK_SPLIT");
-        return !(e && *e && atoi(e) == 0);
-    }();
-    return on && roll_packed(p) && p.B <= 512 * kWavesPerBlock * kPackG;
-}
-int roll_block_threads(const DevParams &p) { return roll_pack_split(p) ? kPack2Block : block_threads(p); }
+// shapes of the two-envs-per-wave rollout (gsm_roll_pair_kernel) and of the
+// one-env rollout's plain instantiation (gsm_roll_seg_kernel kPlain); a shape
+// is in one list at most
+#define GSM_PAIR_SHAPES(X) X(24, 24)
+#define GSM_PLAIN_SHAPES(X) X(6, 6) X(12, 12)
 
-// Whether a launch's arguments hold the common configuration that the
-// rollout's plain instantiation is compiled for (gsm_roll_seg_kernel kPlain);
-// `paced`: its launches carry pace counters (DevParams::Roll::pace, set per
-// launch). GSM_ROLL_PLAIN=0 keeps the generic instantiation everywhere (an
-// A/B knob: the outputs are the same either way).
+// Whether a launch's arguments hold the common configuration that the plain
+// instantiation and the pair kernel are compiled for; `paced`: its launches
+// carry pace counters (DevParams::Roll::pace, set per launch).
 static bool roll_seg_plain(const DevParams &p, bool paced) {
-    static const bool on = [] {
-        const char *e = getenv("GSM_ROLL_PLAIN");
-        return !(e && *e && atoi(e) == 0);
-    }();
-    return on && paced && p.strict == 0 && p.shared_reward == 0 && p.auto_reset == 1 && p.nf_full == 0 &&
+    return paced && p.strict == 0 && p.shared_reward == 0 && p.auto_reset == 1 && p.nf_full == 0 &&
            !(p.max_speed > 0.0f);
 }
 
-// shapes of the two-envs-per-wave rollout (gsm_roll_pair_kernel)
-#define GSM_PAIR_SHAPES(X) X(24, 24)
-// Whether a launch runs gsm_roll_pair_kernel: the plain configuration into the
-// bound buffers, a compiled shape. GSM_ROLL_PAIR=0 keeps the one-env kernel
-// (an A/B knob: the outputs are the same either way).
-bool roll_seg_pair(const DevParams &p, bool slots, bool paced) {
-    static const bool on = [] {
-        const char *e = getenv("GSM_ROLL_PAIR");
-        return !(e && *e && atoi(e) == 0);
-    }();
-    if (!on || slots || p.path != kPathSeg || p.G != 1 || !roll_seg_plain(p, paced)) return false;
-#define GSM_PICK(n, no) if (p.N == n && p.No == no) return true;
-    GSM_PAIR_SHAPES(GSM_PICK)
-#undef GSM_PICK
-    return false;
+// dynamic LDS of gsm_roll_seg_kernel's workgroup: the waves' buffers
+// (roll_lds_wave), then the workgroup's hand-off words
+static size_t roll_seg_lds(const DevParams &p) {
+    return (size_t)kWavesPerBlock * roll_lds_wave(p.N, p.E) + 4 * (6 * kWavesPerBlock + 4);
 }
 
-template <bool kSlots, bool kEager = false>
-static const void *pick_roll_seg(const DevParams &p, bool paced = false) {
-    if constexpr (!kSlots && !kEager) {
-        if (roll_seg_pair(p, false, paced)) {
-#define GSM_PICK(n, no)                                                                       \
-    if (p.N == n && p.No == no) {                                                             \
-        switch (p.action_fmt) {                                                               \
-            case 0: return reinterpret_cast<const void *>(&gsm_roll_pair_kernel<n, no, 0>);   \
-            case 1: return reinterpret_cast<const void *>(&gsm_roll_pair_kernel<n, no, 1>);   \
-            default: return reinterpret_cast<const void *>(&gsm_roll_pair_kernel<n, no, 2>);  \
-        }                                                                                     \
+// The one place that decides what a graph rollout launch of the segmented
+// path runs, first match first:
+//   the plain configuration into the bound buffers, G = 1, 24 agents:
+//       gsm_roll_pair_kernel, two envs per wave;
+//   3 agents: four envs per wave, per-wave hand-off; up to 8192 envs
+//       gsm_roll_pack2_kernel (emission on waves of its own: 512-thread
+//       workgroups, two per CU at most, so 8192 envs fill one residency
+//       round), above that gsm_roll_pack_kernel;
+//   6, 12 and 24 agents: gsm_roll_seg_kernel, one env per wave; its plain
+//       instantiation for the plain configuration into the bound buffers at
+//       6 and 12 agents (at 24 that configuration ran the pair kernel above).
+template <bool kSlots>
+static RollForm pick_roll_seg(const DevParams &p, bool paced) {
+    RollForm f{nullptr, kBlock, kWavesPerBlock, 0, false};
+    const bool plain = !kSlots && roll_seg_plain(p, paced);
+#define GSM_PICK(n, no)                                                              \
+    if (plain && p.G == 1 && p.N == n && p.No == no) {                               \
+        GSM_KERNEL_BY_FMT(f.fn, p.action_fmt, gsm_roll_pair_kernel<n, no, kFmt>)     \
+        f.envs = kPairEnvs;                                                          \
+        f.lds = (size_t)pair_lds_block(p.N, p.No, p.E);                              \
+        return f;                                                                    \
     }
-            GSM_PAIR_SHAPES(GSM_PICK)
+    GSM_PAIR_SHAPES(GSM_PICK)
 #undef GSM_PICK
-        }
+#define GSM_PICK(n, no)                                                                             \
+    if (p.N == n && p.No == no) {                                                                   \
+        f.envs = kWavesPerBlock * kPackG;                                                           \
+        f.per_wave = true;                                                                          \
+        if (p.B <= 512 * kWavesPerBlock * kPackG) {                                                 \
+            GSM_KERNEL_BY_FMT(f.fn, p.action_fmt, gsm_roll_pack2_kernel<n, no, kFmt, kSlots>)       \
+            f.threads = kPack2Block;                                                                \
+            f.lds = (size_t)kWavesPerBlock * pack2_lds_stepper<n, no>() +                           \
+                    4 * kWavesPerBlock * (2 + kPack2Emitters);                                      \
+        } else {                                                                                    \
+            GSM_KERNEL_BY_FMT(f.fn, p.action_fmt, gsm_roll_pack_kernel<n, no, kFmt, kSlots>)        \
+            f.lds = (size_t)kWavesPerBlock * pack_lds_wave<n, no>() + 4 * kWavesPerBlock;           \
+        }                                                                                           \
+        return f;                                                                                   \
     }
-    if constexpr (kEager) {   // (one env per wave only: the packed rollout keeps host epochs)
-        if (roll_packed(p)) return nullptr;
-    } else {
-        const bool split = roll_pack_split(p);
-#define GSM_PICK(n, no)                                                                                     \
-    if (p.N == n && p.No == no) {                                                                           \
-        switch (p.action_fmt) {                                                                             \
-            case 0: return split ? reinterpret_cast<const void *>(&gsm_roll_pack2_kernel<n, no, 0, kSlots>)  \
-                                 : reinterpret_cast<const void *>(&gsm_roll_pack_kernel<n, no, 0, kSlots>);  \
-            case 1: return split ? reinterpret_cast<const void *>(&gsm_roll_pack2_kernel<n, no, 1, kSlots>)  \
-                                 : reinterpret_cast<const void *>(&gsm_roll_pack_kernel<n, no, 1, kSlots>);  \
-            default: return split ? reinterpret_cast<const void *>(&gsm_roll_pack2_kernel<n, no, 2, kSlots>) \
-                                  : reinterpret_cast<const void *>(&gsm_roll_pack_kernel<n, no, 2, kSlots>); \
-        }                                                                                                   \
-    }
-        GSM_PACK_SHAPES(GSM_PICK)
+    GSM_PACK_SHAPES(GSM_PICK)
 #undef GSM_PICK
+    f.lds = roll_seg_lds(p);
+#define GSM_PICK(n, no)                                                                               \
+    if (plain && p.N == n && p.No == no) {                                                            \
+        GSM_KERNEL_BY_FMT(f.fn, p.action_fmt, gsm_roll_seg_kernel<n, no, kFmt, false, false, true>)   \
+        return f;                                                                                     \
     }
-#define GSM_PICK(n, no)                                                                          \
-    if (p.N == n && p.No == no) {                                                                \
-        switch (p.action_fmt) {                                                                  \
-            case 0: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 0, kSlots, kEager>); \
-            case 1: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 1, kSlots, kEager>); \
-            default: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 2, kSlots, kEager>); \
-        }                                                                                        \
-    }
-    // (the plain instantiation for the rollout into the bound buffers only:
-    // the rollout-buffer and eager forms keep the generic one)
-    if constexpr (!kSlots && !kEager) {
-        if (roll_seg_plain(p, paced)) {
-#define GSM_PICK_PLAIN(n, no)                                                                                  \
-    if (p.N == n && p.No == no) {                                                                              \
-        switch (p.action_fmt) {                                                                                \
-            case 0: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 0, false, false, true>);  \
-            case 1: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 1, false, false, true>);  \
-            default: return reinterpret_cast<const void *>(&gsm_roll_seg_kernel<n, no, 2, false, false, true>); \
-        }                                                                                                      \
-    }
-            GSM_ROLL_SHAPES(GSM_PICK_PLAIN)
-#undef GSM_PICK_PLAIN
-        }
+    GSM_PLAIN_SHAPES(GSM_PICK)
+#undef GSM_PICK
+#define GSM_PICK(n, no)                                                                   \
+    if (p.N == n && p.No == no) {                                                         \
+        GSM_KERNEL_BY_FMT(f.fn, p.action_fmt, gsm_roll_seg_kernel<n, no, kFmt, kSlots>)   \
+        return f;                                                                         \
     }
     GSM_ROLL_SHAPES(GSM_PICK)
 #undef GSM_PICK
-    return nullptr;
+    return f;
 }
-const void *roll_seg_kernel_fn(const DevParams &p, bool slots, bool paced) {
-    if (p.path != kPathSeg) return nullptr;
+RollForm roll_seg_form(const DevParams &p, bool slots, bool paced) {
+    if (p.path != kPathSeg) return RollForm{};
     return slots ? pick_roll_seg<true>(p, paced) : pick_roll_seg<false>(p, paced);
 }
-const void *roll_seg_eager_kernel_fn(const DevParams &p) {
-    if (p.path != kPathSeg) return nullptr;
-    return pick_roll_seg<false, true>(p);
-}
-size_t roll_kernel_lds(const DevParams &p, bool pair) {
-    if (pair) return (size_t)pair_lds_block(p.N, p.No, p.E);
-#define GSM_PICK(n, no)                                                                            \
-    if (p.N == n && p.No == no)                                                                     \
-        return roll_pack_split(p) ? (size_t)kWavesPerBlock * pack2_lds_stepper<n, no>() + 4 * kWavesPerBlock * (2 + kPack2Emitters) \
-                                  : (size_t)kWavesPerBlock * pack_lds_wave<n, no>() + 4 * kWavesPerBlock;
-    GSM_PACK_SHAPES(GSM_PICK)
+// (the packed shapes have none: gsm_step runs their step and emit kernels)
+RollForm roll_seg_eager_form(const DevParams &p) {
+    if (p.path != kPathSeg) return RollForm{};
+    RollForm f{nullptr, kBlock, kWavesPerBlock, roll_seg_lds(p), false};
+#define GSM_PICK(n, no) \
+    if (p.N == n && p.No == no) GSM_KERNEL_BY_FMT(f.fn, p.action_fmt, gsm_roll_seg_kernel<n, no, kFmt, false, true>)
+    GSM_ROLL_SHAPES(GSM_PICK)
 #undef GSM_PICK
-    return (size_t)kWavesPerBlock * roll_lds_wave(p.N, p.E) + 4 * (6 * kWavesPerBlock + 4);
+    return f;
 }
 
 const void *emit_seg_kernel_fn(const DevParams &p) {

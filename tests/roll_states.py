@@ -20,7 +20,10 @@ import numpy as np
 # in several (6 and 96 chosen with the oracle: test_roll_states_ref)
 CROWD_L = {24: 0.3, 12: 0.2, 6: 0.15, 3: 0.15, 96: 0.3}
 # the smallest batch that keeps each rollout kernel's layout edges: (N, B)
-SHAPES = {"pair": (24, 9), "generic": (24, 5), "seg12": (12, 5), "seg6": (6, 5), "pack": (3, 37), "tile": (96, 3)}
+# (pack_big: the unsplit packed kernel runs past the split one's 8192 envs;
+# the smallest such batch whose last workgroup is half empty, 8 of 16 envs)
+SHAPES = {"pair": (24, 9), "generic": (24, 5), "seg12": (12, 5), "seg6": (6, 5), "pack": (3, 37),
+          "pack_big": (3, 8200), "tile": (96, 3)}
 B_PARTIAL = 11                  # pair: a second workgroup of three envs, its first no lone half
 K = 5                           # steps of a launch
 K_STAG, EL_STAG = 10, 4         # the staggered cases: launch and episode length

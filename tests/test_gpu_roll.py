@@ -292,13 +292,12 @@ def test_roll_recycled_after_many_replays():
     ref.close()
 
 
-@pytest.mark.parametrize("N,B", [(24, 8192), (3, 4096), (96, 1024), (12, 100), (6, 37)])
+@pytest.mark.parametrize("N,B", [(24, 8192), (12, 100), (6, 37)])
 def test_eager_one_launch_equals_two_kernels(N, B, monkeypatch):
-    """gsm_step as one rollout launch of one step (GSM_EAGER_ONE_LAUNCH=1,
-    where the config has a rollout kernel; the default at 6-24 agents) leaves
-    every buffer exactly as the step kernel + emit kernel pair
-    (GSM_EAGER_ONE_LAUNCH=0) does, over steps with auto-resets,
-    in both the bound buffers and redirected outputs."""
+    """gsm_step as one rollout launch of one step (the default at 6-24
+    agents; the other shapes have no such form) leaves every buffer exactly as
+    the step kernel + emit kernel pair (GSM_EAGER_ONE_LAUNCH=0) does, over
+    steps with auto-resets, in both the bound buffers and redirected outputs."""
     T, EL = 7, 5
     acts = torch.randint(0, 5, (T, B, N), dtype=torch.int32, device=DEV)
     envs = []
@@ -306,7 +305,7 @@ def test_eager_one_launch_equals_two_kernels(N, B, monkeypatch):
         if two:
             monkeypatch.setenv("GSM_EAGER_ONE_LAUNCH", "0")
         else:
-            monkeypatch.setenv("GSM_EAGER_ONE_LAUNCH", "1")
+            monkeypatch.delenv("GSM_EAGER_ONE_LAUNCH", raising=False)
         env, _ = _env(n_agents=N, n_envs=B, episode_length=EL, seed=9)
         env.reset(seed=9)
         for t in range(T):
@@ -320,10 +319,10 @@ def test_eager_one_launch_equals_two_kernels(N, B, monkeypatch):
         e.close()
 
 
-@pytest.mark.parametrize("N,B", [(24, 512), (96, 16), (12, 100)])
+@pytest.mark.parametrize("N,B", [(24, 512), (12, 100)])
 def test_eager_one_launch_redirected_outputs(N, B, monkeypatch):
-    """The one-launch eager step (GSM_EAGER_ONE_LAUNCH=1) writing every output
-    into a fresh redirected set per step (gsm_step_into: node features,
+    """The one-launch eager step (the default at 6-24 agents) writing every
+    output into a fresh redirected set per step (gsm_step_into: node features,
     reward, cost, done, counts, CSR pointers and edges) gives exactly the
     two-kernel pair's outputs of every step, auto-resets included."""
     T, EL = 6, 4
@@ -334,7 +333,7 @@ def test_eager_one_launch_redirected_outputs(N, B, monkeypatch):
         if two:
             monkeypatch.setenv("GSM_EAGER_ONE_LAUNCH", "0")
         else:
-            monkeypatch.setenv("GSM_EAGER_ONE_LAUNCH", "1")
+            monkeypatch.delenv("GSM_EAGER_ONE_LAUNCH", raising=False)
         env, _ = _env(n_agents=N, n_envs=B, episode_length=EL, seed=13)
         env.reset(seed=13)
         steps = []

@@ -9,21 +9,13 @@ a full one (8), more than two (17); launches with one, two, three and five
 steps (the tail alone, with and without loop emissions); the three action
 formats; auto-resets inside the launch, with both halves of a wave resetting
 together and on different steps; two replays of one slot back to back (epoch
-and double-buffer alternation); GSM_ROLL_PAIR=0 in a child process (the
-one-env kernel: same bytes); and a config off the plain defaults, which the
+and double-buffer alternation); and a config off the plain defaults, which the
 generic one-env kernel runs."""
-import hashlib
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = Path(__file__).resolve().parents[1]
 DEV = "cuda:0"
 N = 24
 KEYS = ("pos", "vel", "step_count", "episode", "node_feat", "reward", "cost", "done", "edge_count",
@@ -130,33 +122,6 @@ def test_pair_nonfinite_positions():
     assert bool(torch.isnan(got["pos"][2, 3]).any())
 
 
-def test_pair_off_equals_on_in_a_child_process():
-    """GSM_ROLL_PAIR=0 (read once per process) keeps the one-env kernel: the
-    same bytes in every buffer."""
-    here = _digest()
-    env = dict(os.environ, GSM_ROLL_PAIR="0")
-    r = subprocess.run([sys.executable, str(Path(__file__).resolve())], capture_output=True, text=True, env=env,
-                       timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert r.stdout.strip().splitlines()[-1] == here
-
-
 def test_generic_kernel_keeps_configs_off_the_plain_defaults():
     _check(9, 5, shared_reward=True, episode_length=4)
 
-
-def _digest():
-    B, K = 9, 10
-    env = _env(B, episode_length=4)
-    got = _run(env, _acts(B, K), K, "roll", stagger=True)
-    env.close()
-    hs = hashlib.sha256()
-    for k in sorted(got):
-        hs.update(got[k].cpu().numpy().tobytes())
-    return hs.hexdigest()
-
-
-if __name__ == "__main__":
-    for p in (ROOT, ROOT / "gs-marl_amd"):
-        sys.path.insert(0, str(p))
-    print(_digest())

@@ -72,7 +72,7 @@ def test_crowd_is_crowded(shape):
 
 
 def test_spread_reaches_the_ulp_term():
-    for shape in ("pair", "pack", "tile"):
+    for shape in ("pair", "pack", "pack_big", "tile"):
         N, B = rs.SHAPES[shape]
         st = rs.spread(N, N, B, seed=N)
         far = np.abs(st["pos"]) >= 8.0
@@ -174,7 +174,7 @@ def test_coincident_pairs_persist(shape, where, strict):
         assert np.isnan(s["pos"][envs, :N]).all() and np.isfinite(s["pos"][rest]).all()
 
 
-@pytest.mark.parametrize("shape", ["pair", "pack", "seg12"])
+@pytest.mark.parametrize("shape", ["pair", "pack", "pack_big", "seg12"])
 def test_staggered_relayouts(shape):
     N, B = rs.SHAPES[shape]
     K, EL = rs.K_STAG, rs.EL_STAG

@@ -3,7 +3,8 @@ loop without a sync) against device time per step (the loop with a sync at
 both ends), and the same for bare gsm_step calls through the C-ABI (no
 Python wrapper). Prints one JSON line. Run as
     python tools/probe_eager.py [--steps 2000]
-with GSM_EAGER_ONE_LAUNCH=1 for the one-launch form."""
+for the config's default form (one launch at 6-24 agents, else the step and
+emit kernels), and with GSM_EAGER_ONE_LAUNCH=0 for the two launches."""
 import argparse
 import ctypes as C
 import json
@@ -33,7 +34,8 @@ def main():
     for t in range(200):
         env.step(acts[t % 100], sync_edges=False)
     torch.cuda.synchronize()
-    out = {"config": f"{a.agents}x{a.envs}", "one_launch": os.environ.get("GSM_EAGER_ONE_LAUNCH", "0")}
+    two = os.environ.get("GSM_EAGER_ONE_LAUNCH", "") == "0"
+    out = {"config": f"{a.agents}x{a.envs}", "one_launch": "off (two launches)" if two else "default"}
     for name, fn in (("env_step", lambda t: env.step(acts[t % 100], sync_edges=False)),):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
