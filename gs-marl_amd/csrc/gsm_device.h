@@ -245,6 +245,56 @@ __device__ __forceinline__ float contact_scale(const Params &p, float d2, float 
     return p.cf * pen * __builtin_amdgcn_rcpf(d);
 }
 
+// apply_environment_force's contact terms on agent position `pi`: the
+// colliders of the candidate mask `cm` in ascending order, each one's force
+// added to F. `pos_of(c)` gives collider c's position (as strict_bad);
+// `each(ag, d2)` sees every pair before its force (a collision count).
+template <typename Params, typename Mask, typename PosOf, typename Each>
+__device__ __forceinline__ float2 contact_walk(const Params &pc, float2 F, float2 pi, Mask cm, int N, PosOf pos_of,
+                                               Each each) {
+    // (both constants read before the loop: a per-lane select of the two
+    // kernarg fields compiles to a vector load and a vmcnt wait per contact)
+    const float dmin_aa = pc.dmin_aa, dmin_ao = pc.dmin_ao;
+    while (cm) {
+        const int c = sizeof(Mask) > 4 ? __builtin_ctzll(cm) : __builtin_ctz((uint32_t)cm);
+        cm &= cm - 1;
+        const bool ag = c < N;
+        const float2 pj = pos_of(c);
+        const float dx = pi.x - pj.x, dy = pi.y - pj.y;
+        const float d2 = dx * dx + dy * dy;
+        each(ag, d2);
+        const float f = contact_scale(pc, d2, ag ? dmin_aa : dmin_ao);
+        F.x += f * dx;
+        F.y += f * dy;
+    }
+    return F;
+}
+template <typename Params, typename Mask, typename PosOf>
+__device__ __forceinline__ float2 contact_walk(const Params &pc, float2 F, float2 pi, Mask cm, int N, PosOf pos_of) {
+    return contact_walk(pc, F, pi, cm, N, pos_of, [](bool, float) {});
+}
+
+// integrate_state (App. A S6) for one agent at `pi` under force (Fx, Fy):
+// damping, F / m * dt, the speed clamp (max_speed 0: none; a constant 0 folds
+// it away), v updated in place, the new position returned.
+template <typename Params>
+__device__ __forceinline__ float2 integrate_agent(const Params &pc, float2 &v, float2 pi, float Fx, float Fy,
+                                                  float max_speed) {
+    const float dt = pc.dt;
+    v.x = v.x * pc.omd;
+    v.y = v.y * pc.omd;
+    v.x = v.x + (Fx * pc.inv_mass) * dt;
+    v.y = v.y + (Fy * pc.inv_mass) * dt;
+    if (max_speed > 0.0f) {
+        const float sp = sqrtf(v.x * v.x + v.y * v.y);
+        if (sp > max_speed) {
+            v.x = v.x / sp * max_speed;
+            v.y = v.y / sp * max_speed;
+        }
+    }
+    return make_float2(pi.x + v.x * dt, pi.y + v.y * dt);
+}
+
 // ---- fused rollout hand-offs (gsm_seg_kernels.hip / gsm_tile_kernels.hip)
 typedef __attribute__((address_space(1))) uint64_t gu64;
 typedef __attribute__((address_space(1))) uint32_t gu32;

@@ -870,7 +870,9 @@ __device__ __forceinline__ int seg_env(const DevParams &p, const Shape<kN, kNo> 
             const float2 pi = s_pos[m];
             float Fx = u.x, Fy = u.y;
             uint64_t cm = cand_prev;
-            // (both constants read before the loop: a per-lane select of the
+            // (contact_walk's text written out: through the helper this
+            // kernel's loop compiles differently, profiles/pack_share/README.md;
+            // both constants read before the loop: a per-lane select of the
             // two kernarg fields compiles to a vector load and a vmcnt wait
             // per contact)
             const float dmin_aa = pc.dmin_aa, dmin_ao = pc.dmin_ao;
@@ -889,22 +891,7 @@ __device__ __forceinline__ int seg_env(const DevParams &p, const Shape<kN, kNo> 
                 Fx = __builtin_nanf("");   // App. A S16 strict: MPE's 0/0 force
                 Fy = __builtin_nanf("");
             }
-            const float dt = pc.dt, max_speed = pc.max_speed;
-            v.x = v.x * pc.omd;
-            v.y = v.y * pc.omd;
-            v.x = v.x + (Fx * pc.inv_mass) * dt;
-            v.y = v.y + (Fy * pc.inv_mass) * dt;
-            if (max_speed > 0.0f) {
-                const float sp = sqrtf(v.x * v.x + v.y * v.y);
-                if (sp > max_speed) {
-                    v.x = v.x / sp * max_speed;
-                    v.y = v.y / sp * max_speed;
-                }
-            }
-            float2 np;
-            np.x = pi.x + v.x * dt;
-            np.y = pi.y + v.y * dt;
-            s_pos[m] = np;
+            s_pos[m] = integrate_agent(pc, v, pi, Fx, Fy, pc.max_speed);
         }
         wave_sync();
         t += 1;
@@ -1349,21 +1336,7 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
     // apply_environment_force: the action force plus the contact terms of the
     // candidates in ascending collider order
     auto add_contacts = [&](const float2 *s_pos, float2 F, float2 pi, uint64_t cm, const KernargParams &pc) {
-        // (both constants read before the loop: a per-lane select of the two
-        // kernarg fields compiles to a vector load and a vmcnt wait per contact)
-        const float dmin_aa = pc.dmin_aa, dmin_ao = pc.dmin_ao;
-        while (cm) {
-            const int c = __builtin_ctzll(cm);
-            cm &= cm - 1;
-            const bool ag = c < N;
-            const float2 pj = s_pos[row_entity(c, N)];
-            const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-            const float d2 = dx * dx + dy * dy;
-            const float f = contact_scale(pc, d2, ag ? dmin_aa : dmin_ao);
-            F.x += f * dx;
-            F.y += f * dy;
-        }
-        return F;
+        return contact_walk(pc, F, pi, cm, N, [&](int c) { return s_pos[row_entity(c, N)]; });
     };
     // With the near-bit walk (kFused) each step's sweep forms the next step's
     // force at the positions it reads (obs_sweep_g1 kForce), so the loop runs
@@ -1496,6 +1469,9 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
                 Fx = __builtin_nanf("");
                 Fy = __builtin_nanf("");
             }
+            // (integrate_agent's text written out: through the helper the
+            // 24-agent instantiations compile to another register assignment,
+            // profiles/pack_share/README.md)
             const float dt = pc.dt, max_speed = kPlain ? 0.0f : pc.max_speed;
             v.x = v.x * pc.omd;
             v.y = v.y * pc.omd;
@@ -1946,19 +1922,8 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
     // ascending collider order (gsm_roll_seg_kernel add_contacts)
     if (agent) {
         KernargParams &pc = late_params();
-        float2 F = roll_force<kFmt>(pc, a0, true);
-        const float2 pi = s_buf0[li];
-        const float dmin_aa = pc.dmin_aa, dmin_ao = pc.dmin_ao;
-        for (uint64_t cm = cand_prev; cm; cm &= cm - 1) {
-            const int c = __builtin_ctzll(cm);
-            const float2 pj = s_buf0[row_entity(c, N)];
-            const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-            const float d2 = dx * dx + dy * dy;
-            const float f = contact_scale(pc, d2, c < N ? dmin_aa : dmin_ao);
-            F.x += f * dx;
-            F.y += f * dy;
-        }
-        s_force[li] = F;
+        s_force[li] = contact_walk(pc, roll_force<kFmt>(pc, a0, true), s_buf0[li], cand_prev, N,
+                                   [&](int c) { return s_buf0[row_entity(c, N)]; });
     }
 
     // The sweep of both envs over all M columns from the positions at `sp`
@@ -2228,15 +2193,7 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
         if (agent) {
             const float2 pi = s_cur[li];
             const float2 F = s_force[li];
-            const float dt = pc.dt;
-            v.x = v.x * pc.omd;
-            v.y = v.y * pc.omd;
-            v.x = v.x + (F.x * pc.inv_mass) * dt;
-            v.y = v.y + (F.y * pc.inv_mass) * dt;
-            float2 np;
-            np.x = pi.x + v.x * dt;
-            np.y = pi.y + v.y * dt;
-            s_pos[li] = np;
+            s_pos[li] = integrate_agent(pc, v, pi, F.x, F.y, 0.0f);
         }
         wave_sync();
         t += 1;
@@ -2458,19 +2415,353 @@ __device__ __forceinline__ int seg_scan16(int v) {   // inclusive scan within th
     return v;
 }
 
+// ---- What the two packed rollouts share: gsm_roll_pack_kernel steps and
+// emits on one wave, gsm_roll_pack2_kernel on a wave each. A lane's identity,
+// its env's state in registers, one step in pieces cut where the kernels put
+// work of their own between them, and the emission in two parts. The kernels
+// lay out the LDS: every s_* pointer here is this lane's env's rows of one
+// buffer ([E] positions, [N] forces).
+struct PackLane {
+    int lane, seg, m;             // lane of the wave, its env's 16-lane segment, its row there
+    int ent;                      // the row's collider entity
+    int64_t b, eb;                // its env; the env its addresses are formed from (0 for a dead segment)
+    bool env_live, live, agent;   // the env exists; and the row is a collider; and an agent
+};
+template <int kN, int kNo>
+__device__ __forceinline__ PackLane pack_lane(const DevParams &p, int wave) {
+    static_assert(kN + kNo <= kPackSeg && 2 * kN + kNo <= kPackSeg, "one 16-lane segment per env");
+    PackLane L;
+    L.lane = threadIdx.x & 63;
+    L.seg = L.lane >> 4;
+    L.m = L.lane & (kPackSeg - 1);
+    L.b = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * kPackG + L.seg;
+    L.env_live = L.b < p.B;
+    L.live = L.env_live && L.m < kN + kNo;
+    L.agent = L.live && L.m < kN;
+    L.eb = L.env_live ? L.b : 0;
+    L.ent = L.m < kN ? L.m : kN + L.m;
+    return L;
+}
+// an env's state in every lane of its segment (v, cand: the lane's agent row)
+struct PackState {
+    float2 v, acc;
+    int t, ep;
+    uint32_t cand;   // the contact candidates on the current positions
+    bool coinc;      // the last step's positions hold a coincident agent column
+};
+// what a step's observation leaves for its outputs and its emission
+struct PackObs {
+    float2 pm;             // the row's position after the step (and a re-layout)
+    uint32_t rad, cand;    // radius row bits, contact candidates
+    bool reset;            // the env was re-laid out
+};
+
+// the Xfer view of the kernargs (gsm_device.h: the per-wave CSR hand-off)
+__device__ __forceinline__ Xfer pack_xf() {
+    KernargParams &q = late_params();
+    Xfer x;
+    x.W = q.roll.xW;
+    x.NG = q.roll.xNG;
+    x.agg = q.roll.gran;
+    x.grp = x.agg + (int64_t)q.roll.K * x.W;
+    x.status = q.roll.status;
+    x.etag = roll_epoch_tag(q.roll.epoch);
+    return x;
+}
+
+// One pass over the env's M columns from the positions at `sp` (lane m: row m
+// at pm): radius row bits, contact candidates (agent rows), collisions (agent
+// rows, own column excluded), an agent-column coincidence, and the contact
+// forces of the candidates added to F in ascending collider order (the step
+// kernel's force pass: same operations).
+template <int kN, int kNo>
+__device__ __forceinline__ void pack_sweep(const PackLane &L, const float2 *sp, float2 pm, uint32_t &rad,
+                                           uint32_t &cand, int &cnt, bool &zero_agent, float2 &F) {
+    constexpr int N = kN, M = kN + kNo;
+    const int m = L.m;
+    KernargParams &q = late_params();
+    uint32_t r2b1 = __float_as_uint(q.R2) + 1u;
+    asm volatile("" : "+v"(r2b1));
+    // (the candidate threshold is the PAIR's: agent-agent for agent columns
+    // of an agent row, agent-obstacle otherwise)
+    uint32_t cut_aa = __float_as_uint(q.cut2_aa), cut_ao = __float_as_uint(q.cut2_ao);
+    asm volatile("" : "+v"(cut_aa), "+v"(cut_ao));
+    uint32_t rw = 0, cw = 0, nz = 0;
+#pragma unroll
+    for (int c = M - 1; c >= 0; --c) {   // descending: column c ends at bit c
+        const float2 qc = sp[c < N ? c : N + c];
+        const float dx = pm.x - qc.x, dy = pm.y - qc.y;
+        const uint32_t a = __float_as_uint(__builtin_fabsf(dx * dx) + __builtin_fabsf(dy * dy));
+        const uint32_t na = 0u - a;
+        const uint32_t cb = (c < N && m < N) ? cut_aa : cut_ao;   // c compile-time; m < N per lane
+        rw = __builtin_amdgcn_alignbit(rw, na & (a - r2b1), 31);
+        cw = __builtin_amdgcn_alignbit(cw, na & (a - cb), 31);
+        nz = __builtin_amdgcn_alignbit(nz, na, 31);
+    }
+    constexpr uint32_t colmask = (1u << M) - 1u, amask = (1u << N) - 1u;
+    const uint32_t self = 1u << m;
+    const uint32_t zero = ~nz & colmask & ~self;
+    zero_agent = L.live && (zero & amask) != 0u;
+    rad = L.live ? rw & colmask : 0u;
+    cand = L.agent ? cw & colmask : 0u;
+    int n = L.agent ? __popc(zero) : 0;
+    if (L.agent) {
+        const float dmin2_aa = q.dmin2_aa, dmin2_ao = q.dmin2_ao;
+        F = contact_walk(q, F, pm, cand, N, [&](int c) { return sp[c < N ? c : N + c]; },
+                         [&](bool ag, float d2) { n += d2 < (ag ? dmin2_aa : dmin2_ao) ? 1 : 0; });
+    }
+    cnt = n;
+}
+
+// The state before step t_first into registers and buffer s_pos0, and that
+// step's force into s_force: its action, then the stored candidates.
+template <int kN, int kNo, int kFmt>
+__device__ __forceinline__ PackState pack_load(const DevParams &p, const PackLane &L, float2 *s_pos0,
+                                               float2 *s_force) {
+    constexpr int N = kN, E = 2 * kN + kNo;
+    const int m = L.m;
+    PackState S;
+    const float2 *pos_g = p.pos + L.eb * E;
+    const float2 x = L.env_live && m < E ? pos_g[m] : make_float2(0.0f, 0.0f);   // lane m: entity m
+    S.v = L.agent ? p.vel[L.eb * N + m] : make_float2(0.0f, 0.0f);
+    S.t = L.env_live ? p.step_count[L.eb] : 0;
+    S.ep = L.env_live ? p.episode[L.eb] : 0;
+    S.acc = L.env_live ? p.ep_acc[L.eb] : make_float2(0.0f, 0.0f);
+    S.cand = L.agent ? (uint32_t)p.contact_mask[L.eb * N + m] : 0u;
+    S.coinc = false;
+    const float4 a0 = roll_action_load<kN, kFmt>(p, p.roll.t_first % p.roll.n_actions, L.eb, L.agent ? m : 0);
+    if (L.env_live && m < E) s_pos0[m] = x;
+    wave_sync();
+    KernargParams &q = late_params();
+    const float2 F = roll_force<kFmt>(q, a0, L.agent);
+    // (lane m < N: agent m = entity m)
+    if (L.agent) s_force[m] = contact_walk(q, F, x, S.cand, N, [&](int c) { return s_pos0[c < N ? c : N + c]; });
+    return S;
+}
+
+// apply_environment_force (formed by the previous sweep, in s_force) and
+// integrate_state from s_cur into s_pos, goals and obstacles carried along;
+// then the step counted. Returns whether the env's episode is done.
+template <int kN, int kNo>
+__device__ __forceinline__ bool pack_integrate(const PackLane &L, PackState &S, const float2 *s_cur, float2 *s_pos,
+                                               const float2 *s_force) {
+    constexpr int N = kN, M = kN + kNo, E = 2 * kN + kNo;
+    const int m = L.m;
+    KernargParams &pc = late_params();
+    if (L.agent) {
+        const float2 pi = s_cur[m];
+        const float2 F0 = s_force[m];
+        float Fx = F0.x, Fy = F0.y;
+        if (pc.strict && strict_bad(m, pi, N, M, [&](int c) { return s_cur[c < N ? c : N + c]; })) {
+            Fx = __builtin_nanf("");
+            Fy = __builtin_nanf("");
+        }
+        s_pos[m] = integrate_agent(pc, S.v, pi, Fx, Fy, pc.max_speed);
+    } else if (L.env_live && m < E) {
+        s_pos[m] = s_cur[m];
+    }
+    wave_sync();
+    S.t += 1;
+    return L.env_live && S.t >= pc.EL;
+}
+
+// The observation on the post-physics positions s_pos: the sweep (with the
+// next step's force from `anext`), reward / cost into step k's outputs, the
+// episode's sums, auto-reset (scenario.reset_world for the segments whose env
+// is done, then their sweep again), the coincidence flag, and the next
+// step's force into s_force.
+template <int kN, int kNo, int kFmt, bool kSlots>
+__device__ __forceinline__ PackObs pack_observe(const DevParams &p, const PackLane &L, PackState &S, int k,
+                                                bool done, float4 anext, float2 *s_pos, float2 *s_force) {
+    constexpr int N = kN, E = 2 * kN + kNo;
+    const int m = L.m;
+    PackObs O;
+    O.pm = L.live ? s_pos[L.ent] : make_float2(0.0f, 0.0f);
+    int cnt;
+    bool za;
+    float2 Fn = roll_force<kFmt>(late_params(), anext, L.agent);
+    pack_sweep<kN, kNo>(L, s_pos, O.pm, O.rad, O.cand, cnt, za, Fn);
+    float r = 0.0f;
+    if (L.agent) {
+        const float2 g = s_pos[N + m];
+        const float dx = O.pm.x - g.x, dy = O.pm.y - g.y;
+        r = -__builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+    }
+    float rsum = seg_sum16(r);
+    const int csum = seg_sum16(L.agent ? cnt : 0);
+    {
+        KernargParams &q = late_params();
+        if (L.agent) {
+            (q.ro.rew + (kSlots ? k * q.ro.rc_s : 0) + L.eb * N)[m] = q.shared_reward ? rsum : r;
+            (q.ro.cost + (kSlots ? k * q.ro.rc_s : 0) + L.eb * N)[m] = (float)cnt;
+        }
+        if (q.shared_reward) rsum *= (float)N;
+    }
+    if (L.env_live) {
+        S.acc.x += rsum;
+        S.acc.y += (float)csum;
+    }
+    O.reset = done && late_params().auto_reset;
+    if (O.reset && m == 0) late_params().ep_last[L.b] = S.acc;
+    if (__any(O.reset)) {
+        if (O.reset) {
+            S.ep = S.ep + 1;
+            S.t = 0;
+            S.acc = make_float2(0.0f, 0.0f);
+            S.v = make_float2(0.0f, 0.0f);
+            const uint32_t gid = (uint32_t)(late_params().env_base + L.b);
+            if (m < E) s_pos[m] = layout_pos(p, gid, (uint32_t)S.ep, (uint32_t)m);
+        }
+        wave_sync();
+        if (O.reset) {
+            O.pm = L.live ? s_pos[L.ent] : make_float2(0.0f, 0.0f);
+            Fn = roll_force<kFmt>(late_params(), anext, L.agent);
+            pack_sweep<kN, kNo>(L, s_pos, O.pm, O.rad, O.cand, cnt, za, Fn);
+        }
+    }
+    S.coinc = (seg_sum16(za ? 1 : 0) != 0);
+    S.cand = O.cand;
+    if (L.agent) s_force[m] = Fn;
+    return O;
+}
+
+// Step k's node-feature rows (agent rows every step, goal / obstacle rows on
+// a new layout), done flag and edge count. Returns the wave's edge count.
+template <int kN, int kNo, bool kSlots>
+__device__ __forceinline__ int pack_store_outputs(const PackLane &L, const PackState &S, int k, int K, bool done,
+                                                  const PackObs &O, const float2 *s_pos) {
+    constexpr int N = kN, E = 2 * kN + kNo;
+    const int m = L.m;
+    KernargParams &q = late_params();
+    const bool statics = q.nf_full || O.reset;
+    float *nf = q.ro.nf + (kSlots ? k * q.ro.nf_s : 0) + L.eb * E * 7;
+    if (L.agent) {
+        const float2 g = s_pos[N + m];
+        store_row(nf + m * 7, S.v, O.pm, make_float2(g.x - O.pm.x, g.y - O.pm.y), 0.0f);
+    }
+    if (L.env_live && statics && m >= N && m < E) {
+        const float2 a = s_pos[m];
+        store_row(nf + m * 7, make_float2(0.0f, 0.0f), a, make_float2(0.0f, 0.0f), m < 2 * N ? 1.0f : 2.0f);
+    }
+    const int edges = seg_sum16(L.live ? (int)__popc(O.rad) : 0) + 2 * N;
+    if (L.env_live && m == 0) {
+        (q.ro.done + (kSlots ? k * q.ro.done_s : 0))[L.b] = done ? 1 : 0;
+        if (kSlots || k == K - 1) (q.ro.ecount + (kSlots ? k * q.ro.ec_s : 0))[L.b] = edges;
+    }
+    const int ev = L.env_live ? edges : 0;
+    return __builtin_amdgcn_readlane(ev, 0) + __builtin_amdgcn_readlane(ev, 16) + __builtin_amdgcn_readlane(ev, 32) +
+           __builtin_amdgcn_readlane(ev, 48);
+}
+
+// The edges of step j (positions at `sp`, radius rows `row`) at the wave's
+// offset `woff`, each env after the wave's earlier envs, in two parts with
+// `between()` run between them. First the offsets, step j's edge_ptr
+// (kPtrEveryStep: the bound edge_ptr written by every step, else only by the
+// launch's last), and every position the rows need read into registers (M
+// independent LDS reads in flight at once, no LDS read waited on inside the
+// per-edge chain: with one wave per SIMD nothing else hides those latencies);
+// from there the buffer at `sp` is no longer read. Then the row's edges in
+// column order from those registers.
+template <int kN, int kNo, bool kSlots, bool kPtrEveryStep, typename Between>
+__device__ __forceinline__ void pack_emit(const PackLane &L, int j, int K, const float2 *sp, uint32_t row, int woff,
+                                          Between between) {
+    constexpr int N = kN, M = kN + kNo, E = 2 * kN + kNo;
+    const int m = L.m, seg = L.seg;
+    KernargParams &qs = late_params();
+    // rows in entity order: agent rows (agent columns, own goal, obstacle
+    // columns), goal rows, obstacle rows (agent then obstacle columns)
+    const int c = L.live ? __popc(row) + (L.agent ? 1 : 0) : 0;
+    const int incl = seg_scan16(c);
+    const int a_total = seg_sum16(L.agent ? c : 0);
+    // env totals (segment sums plus the N goal rows) and the wave's
+    // exclusive prefix over its envs
+    const int e_tot = L.env_live ? seg_sum16(c) + N : 0;
+    const int t0 = __builtin_amdgcn_readlane(e_tot, 0), t1 = __builtin_amdgcn_readlane(e_tot, 16),
+              t2 = __builtin_amdgcn_readlane(e_tot, 32);
+    const int before = (seg > 0 ? t0 : 0) + (seg > 1 ? t1 : 0) + (seg > 2 ? t2 : 0);
+    int64_t env_off = (int64_t)woff + before;
+    if (woff < 0) {   // a broken hand-off: never write out of bounds
+        if (L.lane == 0)
+            __hip_atomic_store((gu32 *)qs.roll.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        env_off = qs.ro.cap;
+    }
+    if (L.env_live && m == 0 && (kPtrEveryStep || kSlots || j == K - 1)) {
+        int64_t *const eptr = qs.ro.eptr + (kSlots ? j * qs.ro.ep_s : 0);
+        eptr[L.b] = env_off;
+        if (L.b == qs.B - 1) eptr[qs.B] = env_off + e_tot;
+    }
+    const EdgeSink out = roll_edge_sink<kSlots>(qs, j, K);
+    const int32_t g0 = (int32_t)(L.eb * E);
+    float2 qc[M];
+#pragma unroll
+    for (int cc = 0; cc < M; ++cc) qc[cc] = sp[cc < N ? cc : N + cc];
+    const float2 gq = sp[N + (m < N ? m : 0)];
+    const float2 a = sp[L.ent];
+    between();
+    if (!L.live) return;
+    int64_t o = env_off + (incl - c) + (m >= N ? N : 0);
+    auto put = [&](int64_t at, int dst, float2 qd) {
+        if (at < out.cap) {
+            const float dx = a.x - qd.x, dy = a.y - qd.y;
+            out.index[at] = g0 + L.ent;
+            out.index[out.cap + at] = g0 + dst;
+            out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+        }
+    };
+#pragma unroll
+    for (int cc = 0; cc < N; ++cc)
+        if ((row >> cc) & 1u) put(o++, cc, qc[cc]);
+    if (L.agent) {
+        put(o++, N + m, gq);                                 // agent m -> its goal
+        const float dx = gq.x - a.x, dy = gq.y - a.y;
+        const int64_t at = env_off + a_total + m;            // goal row: goal m -> agent m
+        if (at < out.cap) {
+            out.index[at] = g0 + N + m;
+            out.index[out.cap + at] = g0 + m;
+            out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+        }
+    }
+#pragma unroll
+    for (int cc = N; cc < M; ++cc)
+        if ((row >> cc) & 1u) put(o++, N + cc, qc[cc]);
+}
+
+// The final state from the positions at s_fin (what the next launch or an
+// eager step reads) and the degenerate flags.
+template <int kN, int kNo>
+__device__ __forceinline__ void pack_store_final(const PackLane &L, const PackState &S, const float2 *s_fin,
+                                                 uint32_t last_row) {
+    constexpr int N = kN, M = kN + kNo, E = 2 * kN + kNo;
+    const int m = L.m;
+    KernargParams &q = late_params();
+    if (L.env_live && m < E) q.pos[L.eb * E + m] = s_fin[m];
+    if (L.agent) {
+        q.vel[L.eb * N + m] = S.v;
+        q.contact_mask[L.eb * N + m] = S.cand;
+    }
+    if (L.live) q.row_mask[L.eb * M + m] = last_row;
+    if (L.env_live && m == 0) {
+        q.step_count[L.b] = S.t;
+        q.episode[L.b] = S.ep;
+        q.ep_acc[L.b] = S.acc;
+    }
+    if (q.degenerate) {
+        const bool nf_agent = L.agent && nonfinite2(s_fin[m]);
+        const bool nfe = seg_sum16(nf_agent ? 1 : 0) != 0;
+        if (L.env_live && m == 0)
+            q.degenerate[L.b] = (uint8_t)((S.coinc ? kDegCoincident : 0) | (nfe ? kDegNonfinite : 0));
+    }
+}
+
 // (four envs per wave: C2's 4096 envs are 1024 waves, one per SIMD; up to
 // 128 VGPRs, four waves per SIMD, keep 16384 envs in one residency round)
 template <int kN, int kNo, int kFmt, bool kSlots>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void gsm_roll_pack_kernel(DevParams p) {
-    constexpr int N = kN, M = kN + kNo, E = 2 * kN + kNo;
-    static_assert(M <= kPackSeg && E <= kPackSeg, "one 16-lane segment per env");
+    constexpr int N = kN, E = 2 * kN + kNo;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63, seg = lane >> 4, m = lane & (kPackSeg - 1);
-    const int64_t b = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * kPackG + seg;   // this lane's env
-    const bool env_live = b < p.B;
-    const bool live = env_live && m < M, agent = live && m < N;
-    const int64_t eb = env_live ? b : 0;
+    const PackLane L = pack_lane<kN, kNo>(p, wave);
+    const int lane = L.lane, seg = L.seg;
     // LDS per wave: positions [kPackDepth + 1][G][E] in rotation — buffer
     // `cur` holds the positions before step k, step k writes all of its env's
     // rows into the next (agents integrated, goals / obstacles carried or
@@ -2481,93 +2772,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     auto pos_buf = [&](int i) { return s_w + i * kPackG * E + seg * E; };   // this env's rows in buffer i
     float2 *const s_force = s_w + (kPackDepth + 1) * kPackG * E + seg * N;
     int *s_bc = (int *)(smem + kWavesPerBlock * pack_lds_wave<kN, kNo>());   // [waves]: the last step's counts
-    const int ent = m < N ? m : N + m;                                       // this lane's collider entity
-    const int wid = blockIdx.x * kWavesPerBlock + wave;                     // (diagnostic stamps)
-    (void)wid;
+    const int w = blockIdx.x * kWavesPerBlock + wave;   // this wave's index in the grid (granules, diagnostic stamps)
 
-    // ---- the state before step t_first
-    const float2 *pos_g = p.pos + eb * E;
-    float2 x = env_live && m < E ? pos_g[m] : make_float2(0.0f, 0.0f);   // lane m: entity m
-    float2 v = agent ? p.vel[eb * N + m] : make_float2(0.0f, 0.0f);
-    int t = env_live ? p.step_count[eb] : 0, ep = env_live ? p.episode[eb] : 0;
-    float2 acc = env_live ? p.ep_acc[eb] : make_float2(0.0f, 0.0f);
-    uint32_t cand_prev = agent ? (uint32_t)p.contact_mask[eb * N + m] : 0u;
-    const float4 a0 = roll_action_load<kN, kFmt>(p, p.roll.t_first % p.roll.n_actions, eb, agent ? m : 0);
-    if (env_live && m < E) pos_buf(0)[m] = x;
-    wave_sync();
-
-    // one pass over the env's M columns from the positions at `s` (lane m:
-    // row m): radius row bits, contact candidates (agent rows), collisions
-    // (agent rows, own column excluded), an agent-column coincidence; with
-    // kForce the contact forces of the candidates added to *F in ascending
-    // collider order (the step kernel's force pass: same operations)
-    auto sweep = [&](const float2 *sp, float2 pm, uint32_t &rad, uint32_t &cand, int &cnt, bool &zero_agent,
-                     float2 *F) {
-        KernargParams &q = late_params();
-        uint32_t r2b1 = __float_as_uint(q.R2) + 1u;
-        asm volatile("" : "+v"(r2b1));
-        // (the candidate threshold is the PAIR's: agent-agent for agent columns
-        // of an agent row, agent-obstacle otherwise)
-        uint32_t cut_aa = __float_as_uint(q.cut2_aa), cut_ao = __float_as_uint(q.cut2_ao);
-        asm volatile("" : "+v"(cut_aa), "+v"(cut_ao));
-        uint32_t rw = 0, cw = 0, nz = 0;
-#pragma unroll
-        for (int c = M - 1; c >= 0; --c) {   // descending: column c ends at bit c
-            const float2 qc = sp[c < N ? c : N + c];
-            const float dx = pm.x - qc.x, dy = pm.y - qc.y;
-            const uint32_t a = __float_as_uint(__builtin_fabsf(dx * dx) + __builtin_fabsf(dy * dy));
-            const uint32_t na = 0u - a;
-            const uint32_t cb = (c < N && m < N) ? cut_aa : cut_ao;   // c compile-time; m < N per lane
-            rw = __builtin_amdgcn_alignbit(rw, na & (a - r2b1), 31);
-            cw = __builtin_amdgcn_alignbit(cw, na & (a - cb), 31);
-            nz = __builtin_amdgcn_alignbit(nz, na, 31);
-        }
-        constexpr uint32_t colmask = (1u << M) - 1u, amask = (1u << N) - 1u;
-        const uint32_t self = 1u << m;
-        const uint32_t zero = ~nz & colmask & ~self;
-        zero_agent = live && (zero & amask) != 0u;
-        rad = live ? rw & colmask : 0u;
-        cand = agent ? cw & colmask : 0u;
-        int n = agent ? __popc(zero) : 0;
-        if (agent) {
-            float Fx = F ? F->x : 0.0f, Fy = F ? F->y : 0.0f;
-            const float dmin2_aa = q.dmin2_aa, dmin2_ao = q.dmin2_ao, dmin_aa = q.dmin_aa, dmin_ao = q.dmin_ao;
-            for (uint32_t w = cand; w; w &= w - 1u) {
-                const int c = __builtin_ctz(w);
-                const bool ag = c < N;
-                const float2 qc = sp[ag ? c : N + c];
-                const float dx = pm.x - qc.x, dy = pm.y - qc.y;
-                const float d2 = dx * dx + dy * dy;
-                n += d2 < (ag ? dmin2_aa : dmin2_ao) ? 1 : 0;
-                if (F) {
-                    const float f = contact_scale(q, d2, ag ? dmin_aa : dmin_ao);
-                    Fx += f * dx;
-                    Fy += f * dy;
-                }
-            }
-            if (F) *F = make_float2(Fx, Fy);
-        }
-        cnt = n;
-    };
-
-    {   // the forces of step t_first: its action, then the stored candidates
-        float2 F = roll_force<kFmt>(late_params(), a0, agent);
-        if (agent) {
-            const float2 pi = x;   // lane m < N: agent m = entity m
-            const float dmin_aa = late_params().dmin_aa, dmin_ao = late_params().dmin_ao;
-            for (uint32_t w = cand_prev; w; w &= w - 1u) {
-                const int c = __builtin_ctz(w);
-                const bool ag = c < N;
-                const float2 pj = pos_buf(0)[ag ? c : N + c];
-                const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-                const float d2 = dx * dx + dy * dy;
-                const float f = contact_scale(late_params(), d2, ag ? dmin_aa : dmin_ao);
-                F.x += f * dx;
-                F.y += f * dy;
-            }
-            s_force[m] = F;
-        }
-    }
+    PackState S = pack_load<kN, kNo, kFmt>(p, L, pos_buf(0), s_force);
 
     const int K = p.roll.K, n_act = p.roll.n_actions;
     int arow = p.roll.t_first % n_act;
@@ -2585,243 +2792,67 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     // late with the loads at the iteration's start, or four with them one
     // iteration ahead: the offset still settled in ~1900-2200 cycles per
     // step, profiles/r4_stamps.)
-    const int w = blockIdx.x * kWavesPerBlock + wave;      // this wave's index in the grid
     const bool glast = (w & 63) == 63;                      // publishes its group's sums
-    auto xf = [&]() -> Xfer {
-        KernargParams &q = late_params();
-        Xfer x;
-        x.W = q.roll.xW;
-        x.NG = q.roll.xNG;
-        x.agg = q.roll.gran;
-        x.grp = x.agg + (int64_t)q.roll.K * x.W;
-        x.status = q.roll.status;
-        x.etag = roll_epoch_tag(q.roll.epoch);
-        return x;
-    };
     uint32_t row_m1 = 0, row_m2 = 0, row_m3 = 0, row_m4 = 0, row_m5 = 0;   // radius row bits of steps k - 1 .. k - 5
     int cnt_m1 = 0, cnt_m2 = 0;                                // this wave's edge counts of steps k - 1, k - 2
-    uint32_t cand_keep = cand_prev;
-    bool coinc = false;
     static_assert(kPackDepth == 5, "the row ring below");
     auto ring = [](int i) { return i >= kPackDepth + 1 ? i - (kPackDepth + 1) : i; };
     int cur = 0;   // the buffer holding the positions before step k (those after step k - 5: cur + 2)
 
-    // the edges of step j (positions in buffer `pb`, rows `row`) at the wave's
-    // offset `woff`: each env after the wave's earlier envs
+    // the edges of step j (positions in buffer `pb`), both parts back to back
     auto emit = [&](const int j, const int pb, const uint32_t row, const int woff) {
         GSM_TNOW(te2);
-        KernargParams &qs = late_params();
-        // rows in entity order: agent rows (agent columns, own goal, obstacle
-        // columns), goal rows, obstacle rows (agent then obstacle columns)
-        const int c = live ? __popc(row) + (agent ? 1 : 0) : 0;
-        const int incl = seg_scan16(c);
-        const int a_total = seg_sum16(agent ? c : 0);
-        // env totals (segment sums plus the N goal rows) and the wave's
-        // exclusive prefix over its envs
-        const int e_tot = env_live ? seg_sum16(c) + N : 0;
-        const int t0 = __builtin_amdgcn_readlane(e_tot, 0), t1 = __builtin_amdgcn_readlane(e_tot, 16),
-                  t2 = __builtin_amdgcn_readlane(e_tot, 32);
-        const int before = (seg > 0 ? t0 : 0) + (seg > 1 ? t1 : 0) + (seg > 2 ? t2 : 0);
-        int64_t env_off = (int64_t)woff + before;
-        if (woff < 0) {   // a broken hand-off: never write out of bounds
-            if (lane == 0)
-                __hip_atomic_store((gu32 *)qs.roll.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            env_off = qs.ro.cap;
-        }
-        if (env_live && m == 0) {
-            int64_t *const eptr = qs.ro.eptr + (kSlots ? j * qs.ro.ep_s : 0);
-            eptr[b] = env_off;
-            if (b == qs.B - 1) eptr[qs.B] = env_off + e_tot;
-        }
-        const EdgeSink out = roll_edge_sink<kSlots>(qs, j, K);
-        const float2 *sp = pos_buf(pb);
-        const int32_t g0 = (int32_t)(eb * E);
-        // every column's position read up front (M independent LDS reads in
-        // flight at once), then the row's edges in column order from
-        // registers: no LDS read waited on inside the per-edge chain (one
-        // wave per SIMD here: nothing else hides those latencies)
-        float2 qc[M];
-#pragma unroll
-        for (int cc = 0; cc < M; ++cc) qc[cc] = sp[cc < N ? cc : N + cc];
-        const float2 gq = sp[N + (m < N ? m : 0)];
-        if (live) {
-            int64_t o = env_off + (incl - c) + (m >= N ? N : 0);
-            const float2 a = sp[ent];
-            auto put = [&](int64_t at, int dst, float2 qd) {
-                if (at < out.cap) {
-                    const float dx = a.x - qd.x, dy = a.y - qd.y;
-                    out.index[at] = g0 + ent;
-                    out.index[out.cap + at] = g0 + dst;
-                    out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
-                }
-            };
-#pragma unroll
-            for (int cc = 0; cc < N; ++cc)
-                if ((row >> cc) & 1u) put(o++, cc, qc[cc]);
-            if (agent) {
-                put(o++, N + m, gq);                                 // agent m -> its goal
-                const float dx = gq.x - a.x, dy = gq.y - a.y;
-                const int64_t at = env_off + a_total + m;            // goal row: goal m -> agent m
-                if (at < out.cap) {
-                    out.index[at] = g0 + N + m;
-                    out.index[out.cap + at] = g0 + m;
-                    out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
-                }
-            }
-#pragma unroll
-            for (int cc = N; cc < M; ++cc)
-                if ((row >> cc) & 1u) put(o++, N + cc, qc[cc]);
-        }
-        GSM_ACC(late_params(), wid, 4, te2);   // diagnostic builds: emission
+        pack_emit<kN, kNo, kSlots, true>(L, j, K, pos_buf(pb), row, woff, [] {});
+        GSM_ACC(late_params(), w, 4, te2);   // diagnostic builds: emission
     };
 
-    GSM_RSTAMP(p, wid, 8);
+    GSM_RSTAMP(p, w, 8);
     // the first iteration's next-step actions and hand-off loads (the loads
     // unconditional, at valid addresses: a load under a branch leaves the
     // compiler's count of outstanding loads unknown at the join, and every
     // later wait becomes a full drain)
     int nrow = arow + 1 == n_act ? 0 : arow + 1;
-    float4 anext = roll_action_load<kN, kFmt>(late_params(), nrow, eb, agent ? m : 0);
+    float4 anext = roll_action_load<kN, kFmt>(late_params(), nrow, L.eb, L.agent ? L.m : 0);
     // (the offset loads two iterations ahead: xo for this iteration, xo2 for
     // the next — one iteration of a C2 step was shorter than such a load)
-    XferOff xo = xfer_off_load_all(xf(), 0, w, lane);
-    XferOff xo2 = xfer_off_load_all(xf(), 0, w, lane);
-    uint64_t gl = xfer_grp_load(xf(), 0, w, lane);
+    XferOff xo = xfer_off_load_all(pack_xf(), 0, w, lane);
+    XferOff xo2 = xfer_off_load_all(pack_xf(), 0, w, lane);
+    uint64_t gl = xfer_grp_load(pack_xf(), 0, w, lane);
     for (int k = 0; k < K; ++k) {
         GSM_TNOW(tc0);
-        const float2 *const s_cur = pos_buf(cur);
         float2 *const s_pos = pos_buf(ring(cur + 1));
-        KernargParams &pc = late_params();
-        // apply_environment_force (formed by the previous sweep) + integrate_state;
-        // goals and obstacles carried into the step's buffer
-        if (agent) {
-            const float2 pi = s_cur[m];
-            const float2 F0 = s_force[m];
-            float Fx = F0.x, Fy = F0.y;
-            if (pc.strict && strict_bad(m, pi, N, M, [&](int c) { return s_cur[c < N ? c : N + c]; })) {
-                Fx = __builtin_nanf("");
-                Fy = __builtin_nanf("");
-            }
-            const float dt = pc.dt, max_speed = pc.max_speed;
-            v.x = v.x * pc.omd;
-            v.y = v.y * pc.omd;
-            v.x = v.x + (Fx * pc.inv_mass) * dt;
-            v.y = v.y + (Fy * pc.inv_mass) * dt;
-            if (max_speed > 0.0f) {
-                const float sp = sqrtf(v.x * v.x + v.y * v.y);
-                if (sp > max_speed) {
-                    v.x = v.x / sp * max_speed;
-                    v.y = v.y / sp * max_speed;
-                }
-            }
-            s_pos[m] = make_float2(pi.x + v.x * dt, pi.y + v.y * dt);
-        } else if (env_live && m < E) {
-            s_pos[m] = s_cur[m];
-        }
-        wave_sync();
-        t += 1;
-        const bool done = env_live && t >= pc.EL;
-
-        // observation on the post-physics positions (and the next step's forces)
-        float2 pm = live ? s_pos[ent] : make_float2(0.0f, 0.0f);
-        uint32_t rad, cand;
-        int cnt;
-        bool za;
-        float2 Fn = roll_force<kFmt>(late_params(), anext, agent);
-        sweep(s_pos, pm, rad, cand, cnt, za, &Fn);
-        // reward / cost
-        float r = 0.0f;
-        if (agent) {
-            const float2 g = s_pos[N + m];
-            const float dx = pm.x - g.x, dy = pm.y - g.y;
-            r = -__builtin_amdgcn_sqrtf(dx * dx + dy * dy);
-        }
-        float rsum = seg_sum16(r);
-        const int csum = seg_sum16(agent ? cnt : 0);
-        {
-            KernargParams &q = late_params();
-            if (agent) {
-                (q.ro.rew + (kSlots ? k * q.ro.rc_s : 0) + eb * N)[m] = q.shared_reward ? rsum : r;
-                (q.ro.cost + (kSlots ? k * q.ro.rc_s : 0) + eb * N)[m] = (float)cnt;
-            }
-            if (q.shared_reward) rsum *= (float)N;
-        }
-        if (env_live) {
-            acc.x += rsum;
-            acc.y += (float)csum;
-        }
-        const bool reset = done && late_params().auto_reset;
-        if (reset && m == 0) late_params().ep_last[b] = acc;
-        if (__any(reset)) {
-            // auto-reset: scenario.reset_world for the segments whose env is done
-            if (reset) {
-                ep = ep + 1;
-                t = 0;
-                acc = make_float2(0.0f, 0.0f);
-                v = make_float2(0.0f, 0.0f);
-                const uint32_t gid = (uint32_t)(late_params().env_base + b);
-                if (m < E) s_pos[m] = layout_pos(p, gid, (uint32_t)ep, (uint32_t)m);
-            }
-            wave_sync();
-            if (reset) {
-                pm = live ? s_pos[ent] : make_float2(0.0f, 0.0f);
-                Fn = roll_force<kFmt>(late_params(), anext, agent);
-                sweep(s_pos, pm, rad, cand, cnt, za, &Fn);
-            }
-        }
-        coinc = (seg_sum16(za ? 1 : 0) != 0);
-        if (agent) s_force[m] = Fn;
-
-        // node features: agent rows every step, goal / obstacle rows on a new layout
-        KernargParams &q = late_params();
-        const bool statics = q.nf_full || reset;
-        float *nf = q.ro.nf + (kSlots ? k * q.ro.nf_s : 0) + eb * E * 7;
-        if (agent) {
-            const float2 g = s_pos[N + m];
-            store_row(nf + m * 7, v, pm, make_float2(g.x - pm.x, g.y - pm.y), 0.0f);
-        }
-        if (env_live && statics && m >= N && m < E) {
-            const float2 a = s_pos[m];
-            store_row(nf + m * 7, make_float2(0.0f, 0.0f), a, make_float2(0.0f, 0.0f), m < 2 * N ? 1.0f : 2.0f);
-        }
-        const int edges = seg_sum16(live ? (int)__popc(rad) : 0) + 2 * N;
-        if (env_live && m == 0) {
-            (q.ro.done + (kSlots ? k * q.ro.done_s : 0))[b] = done ? 1 : 0;
-            if (kSlots || k == K - 1) (q.ro.ecount + (kSlots ? k * q.ro.ec_s : 0))[b] = edges;
-        }
+        const bool done = pack_integrate<kN, kNo>(L, S, pos_buf(cur), s_pos, s_force);
+        const PackObs O = pack_observe<kN, kNo, kFmt, kSlots>(p, L, S, k, done, anext, s_pos, s_force);
+        const int wcnt = pack_store_outputs<kN, kNo, kSlots>(L, S, k, K, done, O, s_pos);
+        GSM_ACC(late_params(), w, 0, tc0);   // diagnostic builds: the step's work
+        GSM_TNOW(tc1);
         // publish the wave's count of this step, then (a group's last wave)
         // the group sum of the previous step
-        const int ev = env_live ? edges : 0;
-        const int wcnt = __builtin_amdgcn_readlane(ev, 0) + __builtin_amdgcn_readlane(ev, 16) +
-                         __builtin_amdgcn_readlane(ev, 32) + __builtin_amdgcn_readlane(ev, 48);
-        GSM_ACC(late_params(), wid, 0, tc0);   // diagnostic builds: the step's work
-        GSM_TNOW(tc1);
-        if (lane == 0) xfer_st(xf().agg + (int64_t)k * xf().W + w, xf().tag(k), (uint32_t)wcnt);
-        if (k >= 2 && glast) xfer_grp_publish(xf(), gl, k - 2, w, lane, cnt_m2);
-        GSM_ACC(late_params(), wid, 1, tc1);   // publish
+        if (lane == 0) xfer_st(pack_xf().agg + (int64_t)k * pack_xf().W + w, pack_xf().tag(k), (uint32_t)wcnt);
+        if (k >= 2 && glast) xfer_grp_publish(pack_xf(), gl, k - 2, w, lane, cnt_m2);
+        GSM_ACC(late_params(), w, 1, tc1);   // publish
         // the edges of step k - 5
         if (k >= kPackDepth) {
             GSM_TNOW(te0);
-            const int woff = xfer_off_settle(xf(), xo, k - kPackDepth, w, lane);
-            GSM_ACC(late_params(), wid, 3, te0);   // the offset settled
+            const int woff = xfer_off_settle(pack_xf(), xo, k - kPackDepth, w, lane);
+            GSM_ACC(late_params(), w, 3, te0);   // the offset settled
             emit(k - kPackDepth, ring(cur + 2), row_m5, woff);
         }
         row_m5 = row_m4;
         row_m4 = row_m3;
         row_m3 = row_m2;
         row_m2 = row_m1;
-        row_m1 = rad;
+        row_m1 = O.rad;
         cnt_m2 = cnt_m1;
         cnt_m1 = wcnt;
-        cand_keep = cand;
         cur = ring(cur + 1);
         arow = nrow;
         // the next iteration's next-step actions, then its hand-off loads
         nrow = arow + 1 == n_act ? 0 : arow + 1;
-        anext = roll_action_load<kN, kFmt>(late_params(), nrow, eb, agent ? m : 0);
+        anext = roll_action_load<kN, kFmt>(late_params(), nrow, L.eb, L.agent ? L.m : 0);
         xo = xo2;
-        xo2 = xfer_off_load_all(xf(), k + 2 >= kPackDepth ? k + 2 - kPackDepth : 0, w, lane);
-        gl = xfer_grp_load(xf(), k + 1 >= 2 ? k - 1 : 0, w, lane);
+        xo2 = xfer_off_load_all(pack_xf(), k + 2 >= kPackDepth ? k + 2 - kPackDepth : 0, w, lane);
+        gl = xfer_grp_load(pack_xf(), k + 1 >= 2 ? k - 1 : 0, w, lane);
         wave_sync();
     }
     // the tail: the group sums of the last two steps, then the edges of the
@@ -2832,14 +2863,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     const uint32_t last_row = row_m1;
     for (int k = K; k < K + kPackDepth; ++k) {
         if (k > K) {
-            xo = k == K + 1 ? xo2 : xfer_off_load_all(xf(), k >= kPackDepth ? k - kPackDepth : 0, w, lane);
+            xo = k == K + 1 ? xo2 : xfer_off_load_all(pack_xf(), k >= kPackDepth ? k - kPackDepth : 0, w, lane);
             // (clamped to a step of this launch: the load is unconditional, and
             // past the last step it would read beyond the granule allocation)
-            gl = xfer_grp_load(xf(), min(max(k - 2, 0), K - 1), w, lane);
+            gl = xfer_grp_load(pack_xf(), min(max(k - 2, 0), K - 1), w, lane);
         }
-        if (k - 2 >= 0 && k - 2 < K && glast) xfer_grp_publish(xf(), gl, k - 2, w, lane, cnt_m2);
+        if (k - 2 >= 0 && k - 2 < K && glast) xfer_grp_publish(pack_xf(), gl, k - 2, w, lane, cnt_m2);
         if (k >= kPackDepth)
-            emit(k - kPackDepth, ring(cur + 2), row_m5, xfer_off_settle(xf(), xo, k - kPackDepth, w, lane));
+            emit(k - kPackDepth, ring(cur + 2), row_m5, xfer_off_settle(pack_xf(), xo, k - kPackDepth, w, lane));
         row_m5 = row_m4;
         row_m4 = row_m3;
         row_m3 = row_m2;
@@ -2847,31 +2878,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         cnt_m2 = cnt_m1;
         cur = ring(cur + 1);
     }
-    GSM_RSTAMP(p, wid, 9);
+    GSM_RSTAMP(p, w, 9);
     // the last step's sums in the config's workgroup layout (G = 4: the same
     // 16 envs per workgroup), for the emit launch that may follow
     if (lane == 0) s_bc[wave] = last_cnt;
     __syncthreads();
-    KernargParams &q = late_params();
-    if (threadIdx.x == 0 && K >= 1) q.block_edge_sum[blockIdx.x] = s_bc[0] + s_bc[1] + s_bc[2] + s_bc[3];
-    // the final state (what the next launch or an eager step reads)
-    const float2 *const s_fin = pos_buf(fin);
-    if (env_live && m < E) q.pos[eb * E + m] = s_fin[m];
-    if (agent) {
-        q.vel[eb * N + m] = v;
-        q.contact_mask[eb * N + m] = cand_keep;
-    }
-    if (live) q.row_mask[eb * M + m] = last_row;
-    if (env_live && m == 0) {
-        q.step_count[b] = t;
-        q.episode[b] = ep;
-        q.ep_acc[b] = acc;
-    }
-    if (q.degenerate) {
-        const bool nf_agent = agent && nonfinite2(s_fin[m]);
-        const bool nfe = seg_sum16(nf_agent ? 1 : 0) != 0;
-        if (env_live && m == 0) q.degenerate[b] = (uint8_t)((coinc ? kDegCoincident : 0) | (nfe ? kDegNonfinite : 0));
-    }
+    if (threadIdx.x == 0 && K >= 1) late_params().block_edge_sum[blockIdx.x] = s_bc[0] + s_bc[1] + s_bc[2] + s_bc[3];
+    pack_store_final<kN, kNo>(L, S, pos_buf(fin), last_row);
 }
 
 // ---------------------------------------------------------------------------
@@ -2941,8 +2954,7 @@ template <int kN, int kNo, int kFmt, bool kSlots>
 __global__ __launch_bounds__(kPack2Block) __attribute__((amdgpu_waves_per_eu(2 * (1 + kPack2Emitters)))) void
 gsm_roll_pack2_kernel(
     DevParams p) {
-    constexpr int N = kN, M = kN + kNo, E = 2 * kN + kNo;
-    static_assert(M <= kPackSeg && E <= kPackSeg, "one 16-lane segment per env");
+    constexpr int N = kN, E = 2 * kN + kNo;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool stepper = wv < kWavesPerBlock;
@@ -2950,11 +2962,8 @@ gsm_roll_pack2_kernel(
     // j = par (mod kPack2Emitters)
     const int wave = stepper ? wv : (wv - kWavesPerBlock) % kWavesPerBlock;   // the stepper this wave is, or emits for
     const int par = stepper ? 0 : (wv - kWavesPerBlock) / kWavesPerBlock;
-    const int lane = threadIdx.x & 63, seg = lane >> 4, m = lane & (kPackSeg - 1);
-    const int64_t b = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * kPackG + seg;   // this lane's env
-    const bool env_live = b < p.B;
-    const bool live = env_live && m < M, agent = live && m < N;
-    const int64_t eb = env_live ? b : 0;
+    const PackLane L = pack_lane<kN, kNo>(p, wave);
+    const int lane = L.lane, seg = L.seg;
     // LDS per stepper: positions [kPack2Ring][G][E] (slot (j + 1) % ring holds
     // the positions after step j, slot 0 those before the launch's first
     // step), the next step's forces [G][N], radius row bits [kPack2Ring][64];
@@ -2967,20 +2976,8 @@ gsm_roll_pack2_kernel(
     int *const s_bc = (int *)(smem + kWavesPerBlock * pack2_lds_stepper<kN, kNo>());   // [waves]
     volatile int *const s_done = s_bc + kWavesPerBlock;       // [waves] steps published
     volatile int *const s_emit = s_done + kWavesPerBlock;     // [waves][emitters] last step emitted + 1
-    const int ent = m < N ? m : N + m;                        // this lane's collider entity
     const int w = blockIdx.x * kWavesPerBlock + wave;        // the stepper's index in the grid (granules)
     const int K = p.roll.K;
-    auto xf = [&]() -> Xfer {
-        KernargParams &q = late_params();
-        Xfer x;
-        x.W = q.roll.xW;
-        x.NG = q.roll.xNG;
-        x.agg = q.roll.gran;
-        x.grp = x.agg + (int64_t)q.roll.K * x.W;
-        x.status = q.roll.status;
-        x.etag = roll_epoch_tag(q.roll.epoch);
-        return x;
-    };
     if (lane == 0 && stepper) {
         s_done[wave] = 0;
         for (int e = 0; e < kPack2Emitters; ++e) s_emit[wave * kPack2Emitters + e] = 0;
@@ -2992,172 +2989,44 @@ gsm_roll_pack2_kernel(
     GSM_RSTAMP(p, w, stepper ? 8 : 10);
 
     if (!stepper) {
-        // ---- the emitter: the edges of every step of its stepper's envs
-        auto emit = [&](const int j, const float2 *sp, const uint32_t row, const int woff) {
-            KernargParams &qs = late_params();
-            const int c = live ? __popc(row) + (agent ? 1 : 0) : 0;
-            const int incl = seg_scan16(c);
-            const int a_total = seg_sum16(agent ? c : 0);
-            const int e_tot = env_live ? seg_sum16(c) + N : 0;
-            const int t0 = __builtin_amdgcn_readlane(e_tot, 0), t1 = __builtin_amdgcn_readlane(e_tot, 16),
-                      t2 = __builtin_amdgcn_readlane(e_tot, 32);
-            const int before = (seg > 0 ? t0 : 0) + (seg > 1 ? t1 : 0) + (seg > 2 ? t2 : 0);
-            int64_t env_off = (int64_t)woff + before;
-            if (woff < 0) {   // a broken hand-off: never write out of bounds
-                if (lane == 0)
-                    __hip_atomic_store((gu32 *)qs.roll.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                env_off = qs.ro.cap;
-            }
-            // (the bound edge_ptr holds the last step's offsets: with several
-            // emitters per stepper an earlier step's could land after it, so
-            // in the bound buffers only the last step writes them)
-            if (env_live && m == 0 && (kSlots || j == K - 1)) {
-                int64_t *const eptr = qs.ro.eptr + (kSlots ? j * qs.ro.ep_s : 0);
-                eptr[b] = env_off;
-                if (b == qs.B - 1) eptr[qs.B] = env_off + e_tot;
-            }
-            const EdgeSink out = roll_edge_sink<kSlots>(qs, j, K);
-            const int32_t g0 = (int32_t)(eb * E);
-            float2 qc[M];
-#pragma unroll
-            for (int cc = 0; cc < M; ++cc) qc[cc] = sp[cc < N ? cc : N + cc];
-            const float2 gq = sp[N + (m < N ? m : 0)];
-            const float2 a = sp[ent];
-            return [=](void) {
-                // (the positions are in registers here: the slot may be reused
-                // as soon as the emitted count is out)
-                if (!live) return;
-                int64_t o = env_off + (incl - c) + (m >= N ? N : 0);
-                auto put = [&](int64_t at, int dst, float2 qd) {
-                    if (at < out.cap) {
-                        const float dx = a.x - qd.x, dy = a.y - qd.y;
-                        out.index[at] = g0 + ent;
-                        out.index[out.cap + at] = g0 + dst;
-                        out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
-                    }
-                };
-#pragma unroll
-                for (int cc = 0; cc < N; ++cc)
-                    if ((row >> cc) & 1u) put(o++, cc, qc[cc]);
-                if (agent) {
-                    put(o++, N + m, gq);                                 // agent m -> its goal
-                    const float dx = gq.x - a.x, dy = gq.y - a.y;
-                    const int64_t at = env_off + a_total + m;            // goal row: goal m -> agent m
-                    if (at < out.cap) {
-                        out.index[at] = g0 + N + m;
-                        out.index[out.cap + at] = g0 + m;
-                        out.attr[at] = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
-                    }
-                }
-#pragma unroll
-                for (int cc = N; cc < M; ++cc)
-                    if ((row >> cc) & 1u) put(o++, N + cc, qc[cc]);
-            };
-        };
+        // ---- the emitter: the edges of every step of its stepper's envs.
         // Step j is emitted once the stepper has finished step j + kPack2Lag
         // (or the launch's last): the group sums of step j + 1, published by
         // the groups' last steppers in their iteration j + 3, are then normally
         // complete when this emission's loads for step j + 1 are issued, so the
         // next settle does not re-poll a granule (an uncached round trip each)
-        XferOff xo = xfer_off_load_all(xf(), par < K ? par : 0, w, lane);
+        XferOff xo = xfer_off_load_all(pack_xf(), par < K ? par : 0, w, lane);
         for (int j = par; j < K; j += kPack2Emitters) {
             GSM_TNOW(te0);
             if (!lds_count_wait(s_done + wave, min(j + 1 + GSM_PACK2_LAG, K), late_params().roll.status)) break;
             GSM_ACC(late_params(), w, 3, te0);
             GSM_TNOW(te1);
             const uint32_t row = s_rows[(j % kPack2Ring) * kWave + lane];
-            const int woff = xfer_off_settle(xf(), xo, j, w, lane);
+            const int woff = xfer_off_settle(pack_xf(), xo, j, w, lane);
             GSM_ACC(late_params(), w, 5, te1);
             GSM_TNOW(te2);
             // the next step's offset loads, in flight during this emission
-            xo = xfer_off_load_all(xf(), j + kPack2Emitters < K ? j + kPack2Emitters : j, w, lane);
-            auto write = emit(j, pos_buf((j + 1) % kPack2Ring), row, woff);
-            if (lane == 0) lds_count_st(s_emit + wave * kPack2Emitters + par, j + 1);   // positions in registers
-            write();
+            xo = xfer_off_load_all(pack_xf(), j + kPack2Emitters < K ? j + kPack2Emitters : j, w, lane);
+            // (the bound edge_ptr holds the last step's offsets: with several
+            // emitters per stepper an earlier step's could land after it, so
+            // in the bound buffers only the last step writes them)
+            pack_emit<kN, kNo, kSlots, false>(L, j, K, pos_buf((j + 1) % kPack2Ring), row, woff, [&] {
+                // (the positions are in registers here: the slot may be reused
+                // as soon as the emitted count is out)
+                if (lane == 0) lds_count_st(s_emit + wave * kPack2Emitters + par, j + 1);
+            });
             GSM_ACC(late_params(), w, 4, te2);
         }
         GSM_RSTAMP(p, w, 11);
     } else {
-        // ---- the stepper: gsm_roll_pack_kernel's loop without the emission
-        const float2 *pos_g = p.pos + eb * E;
-        float2 x = env_live && m < E ? pos_g[m] : make_float2(0.0f, 0.0f);
-        float2 v = agent ? p.vel[eb * N + m] : make_float2(0.0f, 0.0f);
-        int t = env_live ? p.step_count[eb] : 0, ep = env_live ? p.episode[eb] : 0;
-        float2 acc = env_live ? p.ep_acc[eb] : make_float2(0.0f, 0.0f);
-        uint32_t cand_prev = agent ? (uint32_t)p.contact_mask[eb * N + m] : 0u;
-        const float4 a0 = roll_action_load<kN, kFmt>(p, p.roll.t_first % p.roll.n_actions, eb, agent ? m : 0);
-        if (env_live && m < E) pos_buf(0)[m] = x;
-        wave_sync();
-        auto sweep = [&](const float2 *sp, float2 pm, uint32_t &rad, uint32_t &cand, int &cnt, bool &zero_agent,
-                         float2 *F) {
-            KernargParams &q = late_params();
-            uint32_t r2b1 = __float_as_uint(q.R2) + 1u;
-            asm volatile("" : "+v"(r2b1));
-            uint32_t cut_aa = __float_as_uint(q.cut2_aa), cut_ao = __float_as_uint(q.cut2_ao);
-            asm volatile("" : "+v"(cut_aa), "+v"(cut_ao));
-            uint32_t rw = 0, cw = 0, nz = 0;
-#pragma unroll
-            for (int c = M - 1; c >= 0; --c) {
-                const float2 qc = sp[c < N ? c : N + c];
-                const float dx = pm.x - qc.x, dy = pm.y - qc.y;
-                const uint32_t a = __float_as_uint(__builtin_fabsf(dx * dx) + __builtin_fabsf(dy * dy));
-                const uint32_t na = 0u - a;
-                const uint32_t cb = (c < N && m < N) ? cut_aa : cut_ao;
-                rw = __builtin_amdgcn_alignbit(rw, na & (a - r2b1), 31);
-                cw = __builtin_amdgcn_alignbit(cw, na & (a - cb), 31);
-                nz = __builtin_amdgcn_alignbit(nz, na, 31);
-            }
-            constexpr uint32_t colmask = (1u << M) - 1u, amask = (1u << N) - 1u;
-            const uint32_t self = 1u << m;
-            const uint32_t zero = ~nz & colmask & ~self;
-            zero_agent = live && (zero & amask) != 0u;
-            rad = live ? rw & colmask : 0u;
-            cand = agent ? cw & colmask : 0u;
-            int n = agent ? __popc(zero) : 0;
-            if (agent) {
-                float Fx = F ? F->x : 0.0f, Fy = F ? F->y : 0.0f;
-                const float dmin2_aa = q.dmin2_aa, dmin2_ao = q.dmin2_ao, dmin_aa = q.dmin_aa, dmin_ao = q.dmin_ao;
-                for (uint32_t wd = cand; wd; wd &= wd - 1u) {
-                    const int c = __builtin_ctz(wd);
-                    const bool ag = c < N;
-                    const float2 qc = sp[ag ? c : N + c];
-                    const float dx = pm.x - qc.x, dy = pm.y - qc.y;
-                    const float d2 = dx * dx + dy * dy;
-                    n += d2 < (ag ? dmin2_aa : dmin2_ao) ? 1 : 0;
-                    if (F) {
-                        const float f = contact_scale(q, d2, ag ? dmin_aa : dmin_ao);
-                        Fx += f * dx;
-                        Fy += f * dy;
-                    }
-                }
-                if (F) *F = make_float2(Fx, Fy);
-            }
-            cnt = n;
-        };
-        {   // the forces of step t_first: its action, then the stored candidates
-            float2 F = roll_force<kFmt>(late_params(), a0, agent);
-            if (agent) {
-                const float2 pi = x;
-                const float dmin_aa = late_params().dmin_aa, dmin_ao = late_params().dmin_ao;
-                for (uint32_t wd = cand_prev; wd; wd &= wd - 1u) {
-                    const int c = __builtin_ctz(wd);
-                    const bool ag = c < N;
-                    const float2 pj = pos_buf(0)[ag ? c : N + c];
-                    const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-                    const float d2 = dx * dx + dy * dy;
-                    const float f = contact_scale(late_params(), d2, ag ? dmin_aa : dmin_ao);
-                    F.x += f * dx;
-                    F.y += f * dy;
-                }
-                s_force[m] = F;
-            }
-        }
+        // ---- the stepper: gsm_roll_pack_kernel's loop, each step handed to
+        // the emitter instead of emitted
+        PackState S = pack_load<kN, kNo, kFmt>(p, L, pos_buf(0), s_force);
         const int n_act = p.roll.n_actions;
         int arow = p.roll.t_first % n_act;
         const bool glast = (w & 63) == 63;
         int cnt_m1 = 0, cnt_m2 = 0;
-        uint32_t cand_keep = cand_prev, last_row = 0;
-        bool coinc = false;
+        uint32_t last_row = 0;
         // The next steps' actions are loaded GSM_PACK2_APREF steps ahead: in
         // gsm_roll_pack_kernel the emission filled the time between an action
         // load and its use in the next iteration's sweep; without it a load one
@@ -3167,12 +3036,11 @@ gsm_roll_pack2_kernel(
 #pragma unroll
         for (int d = 0; d < GSM_PACK2_APREF; ++d) {
             prow = prow + 1 == n_act ? 0 : prow + 1;
-            apf[d] = roll_action_load<kN, kFmt>(late_params(), prow, eb, agent ? m : 0);
+            apf[d] = roll_action_load<kN, kFmt>(late_params(), prow, L.eb, L.agent ? L.m : 0);
         }
-        uint64_t gl = xfer_grp_load(xf(), 0, w, lane);
+        uint64_t gl = xfer_grp_load(pack_xf(), 0, w, lane);
         for (int k = 0; k < K; ++k) {
             const float4 anext = apf[0];   // step k + 1's actions
-            const float2 *const s_cur = pos_buf(k % kPack2Ring);
             float2 *const s_pos = pos_buf((k + 1) % kPack2Ring);
             // the slot about to be written held step k + 1 - ring's positions:
             // emitted before it is reused
@@ -3184,143 +3052,34 @@ gsm_roll_pack2_kernel(
             }
             GSM_ACC(late_params(), w, 2, tw0);
             GSM_TNOW(tc0);
-            KernargParams &pc = late_params();
-            if (agent) {
-                const float2 pi = s_cur[m];
-                const float2 F0 = s_force[m];
-                float Fx = F0.x, Fy = F0.y;
-                if (pc.strict && strict_bad(m, pi, N, M, [&](int c) { return s_cur[c < N ? c : N + c]; })) {
-                    Fx = __builtin_nanf("");
-                    Fy = __builtin_nanf("");
-                }
-                const float dt = pc.dt, max_speed = pc.max_speed;
-                v.x = v.x * pc.omd;
-                v.y = v.y * pc.omd;
-                v.x = v.x + (Fx * pc.inv_mass) * dt;
-                v.y = v.y + (Fy * pc.inv_mass) * dt;
-                if (max_speed > 0.0f) {
-                    const float sp = sqrtf(v.x * v.x + v.y * v.y);
-                    if (sp > max_speed) {
-                        v.x = v.x / sp * max_speed;
-                        v.y = v.y / sp * max_speed;
-                    }
-                }
-                s_pos[m] = make_float2(pi.x + v.x * dt, pi.y + v.y * dt);
-            } else if (env_live && m < E) {
-                s_pos[m] = s_cur[m];
-            }
-            wave_sync();
-            t += 1;
-            const bool done = env_live && t >= pc.EL;
-            float2 pm = live ? s_pos[ent] : make_float2(0.0f, 0.0f);
-            uint32_t rad, cand;
-            int cnt;
-            bool za;
-            float2 Fn = roll_force<kFmt>(late_params(), anext, agent);
-            sweep(s_pos, pm, rad, cand, cnt, za, &Fn);
-            float r = 0.0f;
-            if (agent) {
-                const float2 g = s_pos[N + m];
-                const float dx = pm.x - g.x, dy = pm.y - g.y;
-                r = -__builtin_amdgcn_sqrtf(dx * dx + dy * dy);
-            }
-            float rsum = seg_sum16(r);
-            const int csum = seg_sum16(agent ? cnt : 0);
-            {
-                KernargParams &q = late_params();
-                if (agent) {
-                    (q.ro.rew + (kSlots ? k * q.ro.rc_s : 0) + eb * N)[m] = q.shared_reward ? rsum : r;
-                    (q.ro.cost + (kSlots ? k * q.ro.rc_s : 0) + eb * N)[m] = (float)cnt;
-                }
-                if (q.shared_reward) rsum *= (float)N;
-            }
-            if (env_live) {
-                acc.x += rsum;
-                acc.y += (float)csum;
-            }
-            const bool reset = done && late_params().auto_reset;
-            if (reset && m == 0) late_params().ep_last[b] = acc;
-            if (__any(reset)) {
-                if (reset) {
-                    ep = ep + 1;
-                    t = 0;
-                    acc = make_float2(0.0f, 0.0f);
-                    v = make_float2(0.0f, 0.0f);
-                    const uint32_t gid = (uint32_t)(late_params().env_base + b);
-                    if (m < E) s_pos[m] = layout_pos(p, gid, (uint32_t)ep, (uint32_t)m);
-                }
-                wave_sync();
-                if (reset) {
-                    pm = live ? s_pos[ent] : make_float2(0.0f, 0.0f);
-                    Fn = roll_force<kFmt>(late_params(), anext, agent);
-                    sweep(s_pos, pm, rad, cand, cnt, za, &Fn);
-                }
-            }
-            coinc = (seg_sum16(za ? 1 : 0) != 0);
-            if (agent) s_force[m] = Fn;
+            const bool done = pack_integrate<kN, kNo>(L, S, pos_buf(k % kPack2Ring), s_pos, s_force);
+            const PackObs O = pack_observe<kN, kNo, kFmt, kSlots>(p, L, S, k, done, anext, s_pos, s_force);
             // the step's row bits for the emitter, then the step published to it
-            s_rows[(k % kPack2Ring) * kWave + lane] = rad;
+            s_rows[(k % kPack2Ring) * kWave + lane] = O.rad;
             if (lane == 0) lds_count_st(s_done + wave, k + 1);
-            KernargParams &q = late_params();
-            const bool statics = q.nf_full || reset;
-            float *nf = q.ro.nf + (kSlots ? k * q.ro.nf_s : 0) + eb * E * 7;
-            if (agent) {
-                const float2 g = s_pos[N + m];
-                store_row(nf + m * 7, v, pm, make_float2(g.x - pm.x, g.y - pm.y), 0.0f);
-            }
-            if (env_live && statics && m >= N && m < E) {
-                const float2 a = s_pos[m];
-                store_row(nf + m * 7, make_float2(0.0f, 0.0f), a, make_float2(0.0f, 0.0f), m < 2 * N ? 1.0f : 2.0f);
-            }
-            const int edges = seg_sum16(live ? (int)__popc(rad) : 0) + 2 * N;
-            if (env_live && m == 0) {
-                (q.ro.done + (kSlots ? k * q.ro.done_s : 0))[b] = done ? 1 : 0;
-                if (kSlots || k == K - 1) (q.ro.ecount + (kSlots ? k * q.ro.ec_s : 0))[b] = edges;
-            }
-            const int ev = env_live ? edges : 0;
-            const int wcnt = __builtin_amdgcn_readlane(ev, 0) + __builtin_amdgcn_readlane(ev, 16) +
-                             __builtin_amdgcn_readlane(ev, 32) + __builtin_amdgcn_readlane(ev, 48);
+            const int wcnt = pack_store_outputs<kN, kNo, kSlots>(L, S, k, K, done, O, s_pos);
             GSM_ACC(late_params(), w, 0, tc0);
             GSM_TNOW(tc1);
-            if (lane == 0) xfer_st(xf().agg + (int64_t)k * xf().W + w, xf().tag(k), (uint32_t)wcnt);
-            if (k >= 2 && glast) xfer_grp_publish(xf(), gl, k - 2, w, lane, cnt_m2);
+            if (lane == 0) xfer_st(pack_xf().agg + (int64_t)k * pack_xf().W + w, pack_xf().tag(k), (uint32_t)wcnt);
+            if (k >= 2 && glast) xfer_grp_publish(pack_xf(), gl, k - 2, w, lane, cnt_m2);
             GSM_ACC(late_params(), w, 1, tc1);
             cnt_m2 = cnt_m1;
             cnt_m1 = wcnt;
-            cand_keep = cand;
-            last_row = rad;
+            last_row = O.rad;
 #pragma unroll
             for (int d = 0; d + 1 < GSM_PACK2_APREF; ++d) apf[d] = apf[d + 1];
             prow = prow + 1 == n_act ? 0 : prow + 1;
-            apf[GSM_PACK2_APREF - 1] = roll_action_load<kN, kFmt>(late_params(), prow, eb, agent ? m : 0);
-            gl = xfer_grp_load(xf(), k + 1 >= 2 ? k - 1 : 0, w, lane);
+            apf[GSM_PACK2_APREF - 1] = roll_action_load<kN, kFmt>(late_params(), prow, L.eb, L.agent ? L.m : 0);
+            gl = xfer_grp_load(pack_xf(), k + 1 >= 2 ? k - 1 : 0, w, lane);
             wave_sync();
         }
         // the group sums of the last two steps (the first's load issued by the loop)
         for (int k = K; k < K + 2; ++k) {
-            if (k > K) gl = xfer_grp_load(xf(), min(max(k - 2, 0), K - 1), w, lane);
-            if (k - 2 >= 0 && k - 2 < K && glast) xfer_grp_publish(xf(), gl, k - 2, w, lane, cnt_m2);
+            if (k > K) gl = xfer_grp_load(pack_xf(), min(max(k - 2, 0), K - 1), w, lane);
+            if (k - 2 >= 0 && k - 2 < K && glast) xfer_grp_publish(pack_xf(), gl, k - 2, w, lane, cnt_m2);
             cnt_m2 = cnt_m1;
         }
-        // the final state (what the next launch or an eager step reads)
-        KernargParams &q = late_params();
-        const float2 *const s_fin = pos_buf(K % kPack2Ring);
-        if (env_live && m < E) q.pos[eb * E + m] = s_fin[m];
-        if (agent) {
-            q.vel[eb * N + m] = v;
-            q.contact_mask[eb * N + m] = cand_keep;
-        }
-        if (live) q.row_mask[eb * M + m] = last_row;
-        if (env_live && m == 0) {
-            q.step_count[b] = t;
-            q.episode[b] = ep;
-            q.ep_acc[b] = acc;
-        }
-        if (q.degenerate) {
-            const bool nf_agent = agent && nonfinite2(s_fin[m]);
-            const bool nfe = seg_sum16(nf_agent ? 1 : 0) != 0;
-            if (env_live && m == 0) q.degenerate[b] = (uint8_t)((coinc ? kDegCoincident : 0) | (nfe ? kDegNonfinite : 0));
-        }
+        pack_store_final<kN, kNo>(L, S, pos_buf(K % kPack2Ring), last_row);
         if (lane == 0) s_bc[wave] = cnt_m1;   // the last step's count
         GSM_RSTAMP(p, w, 9);
     }

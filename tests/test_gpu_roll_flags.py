@@ -7,8 +7,14 @@ launch's arguments. Here one flag at a time is moved off its default, so both
 forms run, at shapes whose last workgroup is partial (B is no multiple of 4),
 with several in-launch re-layouts (T > 2 * episode length) and with at least
 three steps (the loop, both tail emissions, and the edge-list scan kept from
-two iterations back). Every case is compared bit for bit, over every state and
-output buffer, with the per-step chain of the same actions (step kernels and
+two iterations back). The packed kernels of the 3-agent shape take the same
+flags as run-time branches of one instantiation per action format:
+gsm_roll_pack2_kernel (stepper and emitter waves) at 9 envs (a wave with one
+live env, a dead wave, more steps than the emission ring has slots) and at
+1040 envs (260 waves, more than one 64-wave group), gsm_roll_pack_kernel past
+8192 envs (a half-dead last workgroup, more steps than its emission lags, so
+the in-loop emission and the tail both run). Every case is compared bit for
+bit, over every state and output buffer, with the per-step chain of the same actions (step kernels and
 emit kernel: other code than the rollout kernel). (A reset layout holds no
 coincident pair, so the strict case runs the strict instantiation on inputs
 where it equals the default; test_gpu_roll_states.py runs it on coincident
@@ -27,7 +33,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 KEYS = ("pos", "vel", "step_count", "episode", "node_feat", "reward", "cost", "done", "edge_count",
         "edge_ptr", "ep_acc", "ep_last", "row_mask", "contact_mask")
-SHAPES = [(24, 5, 7, 3), (12, 5, 6, 2), (6, 9, 7, 3)]   # N, B, T, episode length
+SHAPES = [(24, 5, 7, 3), (12, 5, 6, 2), (6, 9, 7, 3),   # N, B, T, episode length
+          (3, 9, 11, 3), (3, 1040, 11, 3), (3, 8200, 7, 3)]
 MAX_SPEED = 0.3
 FLAGS = {"default": {}, "shared_reward": dict(shared_reward=True), "no_auto_reset": dict(auto_reset=False),
          "max_speed": dict(max_speed=MAX_SPEED), "strict": dict(strict_degenerate=True)}

@@ -136,8 +136,9 @@ def test_crowd_generic_kernel_equals_chain(flag):
 
 
 @pytest.mark.parametrize("fmt", ["onehot", "cont"])
-def test_crowd_action_formats(fmt):
-    N, B, st = _crowd("pair")
+@pytest.mark.parametrize("shape", ["pair", "pack", "pack_big"])
+def test_crowd_action_formats(shape, fmt):
+    N, B, st = _crowd(shape)
     _check(N, B, st, fmt=fmt, seed=N + B, episode_length=1000)
 
 
