@@ -1534,11 +1534,9 @@ int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, co
     return GSM_OK;
 }
 
-int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
-                 int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
-                 const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels, float scale,
-                 int32_t flags, int32_t n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status,
-                 void *stream) {
+// the shape limits the fused first layer's forward and backward share
+static int env_conv_shape(int64_t n_envs, int32_t n_entities, int64_t edge_limit, int64_t edge_row_stride,
+                          int32_t heads, int32_t channels, int32_t flags, int32_t n_rows_out) {
     const int64_t lim = (int64_t)1 << 31;
     if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
         return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
@@ -1551,6 +1549,17 @@ int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t 
     if (edge_limit < 0 || edge_limit >= lim) return fail(nullptr, GSM_EINVAL, "edge_limit must be in [0, 2^31)");
     if (edge_row_stride < edge_limit) return fail(nullptr, GSM_EINVAL, "edge_row_stride must be >= edge_limit");
     if (flags & ~GSM_CONV_SKIP) return fail(nullptr, GSM_EINVAL, "unknown flags");
+    return GSM_OK;
+}
+
+static int env_conv_forward(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                            int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                            const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels,
+                            float scale, int32_t flags, int32_t n_rows_out, float *out, float *lse, bool want_lse,
+                            int64_t *row_ptr_out, int32_t *status, void *stream, const char *what) {
+    if (const int rc = env_conv_shape(n_envs, n_entities, edge_limit, edge_row_stride, heads, channels, flags,
+                                      n_rows_out))
+        return rc;
     if (!status) return fail(nullptr, GSM_EINVAL, "status is NULL");
     hipStream_t s = as_stream(stream);
     if (n_envs == 0) {
@@ -1560,14 +1569,76 @@ int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t 
         }
         return GSM_OK;
     }
-    if (!node_feat || !edge_ptr || !w || !out) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    if (!node_feat || !edge_ptr || !w || !out || (want_lse && !lse))
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
     if (edge_limit > 0 && (!edge_index || (w_e && !edge_attr)))
         return fail(nullptr, GSM_EINVAL, "edge_index or edge_attr is NULL");
     if ((uintptr_t)w % 16) return fail(nullptr, GSM_EINVAL, "w must be 16-byte aligned");
     const hipError_t e = gsm::launch_env_conv(node_feat, edge_ptr, edge_index, edge_row_stride, edge_attr, edge_limit,
                                               w, w_e, n_envs, n_entities, heads * channels, channels, scale,
-                                              (flags & GSM_CONV_SKIP) != 0, n_rows_out, out, row_ptr_out, status, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv launch");
+                                              (flags & GSM_CONV_SKIP) != 0, n_rows_out, out, lse, row_ptr_out,
+                                              status, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, what);
+    return GSM_OK;
+}
+
+int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                 int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                 const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels, float scale,
+                 int32_t flags, int32_t n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status,
+                 void *stream) {
+    return env_conv_forward(node_feat, edge_ptr, edge_index, edge_row_stride, edge_attr, edge_limit, w, w_e, n_envs,
+                            n_entities, heads, channels, scale, flags, n_rows_out, out, nullptr, false, row_ptr_out,
+                            status, stream, "gsm_env_conv launch");
+}
+
+int gsm_env_conv_fwd(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                     int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                     const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels,
+                     float scale, int32_t flags, int32_t n_rows_out, float *out, float *lse, int64_t *row_ptr_out,
+                     int32_t *status, void *stream) {
+    return env_conv_forward(node_feat, edge_ptr, edge_index, edge_row_stride, edge_attr, edge_limit, w, w_e, n_envs,
+                            n_entities, heads, channels, scale, flags, n_rows_out, out, lse, true, row_ptr_out,
+                            status, stream, "gsm_env_conv_fwd launch");
+}
+
+int gsm_env_conv_backward_work_floats(int64_t n_envs, int32_t n_entities, int64_t edge_limit, int32_t heads,
+                                      int32_t channels, int32_t flags, int64_t *n_floats) {
+    if (const int rc = env_conv_shape(n_envs, n_entities, edge_limit, edge_limit, heads, channels, flags, 1)) return rc;
+    if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
+    *n_floats = gsm::env_conv_backward_work_floats(edge_limit, heads, heads * channels, (flags & GSM_CONV_SKIP) != 0);
+    return GSM_OK;
+}
+
+int gsm_env_conv_bwd(const float *grad_out, const float *node_feat, const int64_t *edge_ptr,
+                     const int32_t *edge_index, int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit,
+                     const float *w, const float *w_e, const float *out, const float *lse, int64_t n_envs,
+                     int32_t n_entities, int32_t heads, int32_t channels, float scale, int32_t flags,
+                     int32_t n_rows_out, float *work, float *dw, float *dw_e, int32_t *status, void *stream) {
+    if (const int rc = env_conv_shape(n_envs, n_entities, edge_limit, edge_row_stride, heads, channels, flags,
+                                      n_rows_out))
+        return rc;
+    if (!status || !dw) return fail(nullptr, GSM_EINVAL, "status or dw is NULL");
+    if (dw_e && !w_e) return fail(nullptr, GSM_EINVAL, "dw_e needs w_e");
+    hipStream_t s = as_stream(stream);
+    const bool skip = (flags & GSM_CONV_SKIP) != 0;
+    const size_t row = sizeof(float) * (size_t)(heads * channels);
+    if (n_envs == 0) {
+        hipError_t e = hipMemsetAsync(dw, 0, row * 8 * (skip ? 4 : 3), s);
+        if (dw_e && e == hipSuccess) e = hipMemsetAsync(dw_e, 0, row, s);
+        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv_bwd memset");
+        return GSM_OK;
+    }
+    if (!grad_out || !node_feat || !edge_ptr || !w || !out || !lse || !work)
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    if (edge_limit > 0 && (!edge_index || (w_e && !edge_attr)))
+        return fail(nullptr, GSM_EINVAL, "edge_index or edge_attr is NULL");
+    if ((uintptr_t)w % 16) return fail(nullptr, GSM_EINVAL, "w must be 16-byte aligned");
+    const hipError_t e = gsm::launch_env_conv_backward(grad_out, node_feat, edge_ptr, edge_index, edge_row_stride,
+                                                       edge_attr, edge_limit, w, w_e, out, lse, n_envs, n_entities,
+                                                       heads * channels, channels, scale, skip, n_rows_out, work,
+                                                       dw, dw_e, status, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv_bwd launch");
     return GSM_OK;
 }
 

@@ -787,6 +787,7 @@ struct ConvParams {
     int B, E, epb, HC, C, skip, n_rows_out;
     float scale;
     float *out;
+    float *lse;                                 // [B][n_rows_out][H] softmax statistics, or nullptr
     int64_t *row_ptr_out;
     int32_t *status;
 };
@@ -844,24 +845,15 @@ __device__ __forceinline__ typename VecT<kVec>::T conv_project(const float (&wr)
     return r;
 }
 
-// the table form is held to 128 VGPRs (four waves a SIMD); the recompute form
-// keeps all four weight blocks in registers at two
-template <int kLP, int kVec, bool kTable>
-__global__ __launch_bounds__(kConvThreads, kTable ? 4 : 2) void gsm_env_conv_kernel(const ConvParams p) {
-    using V = VecT<kVec>;
-    using T = typename V::T;
-    constexpr int kNPP = kConvThreads / kLP;                 // output rows per pass of the block
-    extern __shared__ float4 conv_smem[];
-    char *sm = (char *)conv_smem;
-    const int E = p.E, HC = p.HC;
-    const ConvLds L = conv_lds(p.epb, E, HC, kTable);
+// ranges, rows and entries of envs b0 .. b0+ne-1 -> LDS (est, ecnt, ebad, xs,
+// rs), the checks' bits -> status; shared by the forward and the backward, so
+// an env is edgeless in both or in neither. Ends on a barrier.
+__device__ __forceinline__ void conv_stage_envs(const ConvParams &p, const ConvLds &L, char *sm, int b0, int ne,
+                                                int tid) {
+    const int E = p.E, n_loc = ne * E;
     float *xs = (float *)(sm + L.xs);
     int64_t *est = (int64_t *)(sm + L.est);
     int *ecnt = (int *)(sm + L.ecnt), *ebad = (int *)(sm + L.ebad), *rs = (int *)(sm + L.rs);
-    float *ktab = (float *)(sm + L.tab), *vtab = ktab + p.epb * E * HC;
-    const int tid = threadIdx.x;
-    const int b0 = blockIdx.x * p.epb;                       // grid = ceil(B / epb): b0 < B
-    const int ne = min(p.epb, p.B - b0), n_loc = ne * E;
     int bits = 0;
 
     // ranges: every offset checked before it bounds a loop or forms an address
@@ -911,6 +903,31 @@ __global__ __launch_bounds__(kConvThreads, kTable ? 4 : 2) void gsm_env_conv_ker
     __syncthreads();
     if (tid < ne && ebad[tid]) bits |= GSM_BATCH_OUT_OF_ENV;
     if (bits) atomicOr(p.status, bits);
+}
+
+// the table form is held to 128 VGPRs (four waves a SIMD); the recompute form
+// keeps all four weight blocks in registers at two. kLse (gsm_env_conv_fwd) is
+// the same kernel with one more store, the rows' softmax statistics; that
+// store takes the table form to 132 VGPRs, three waves, so it is a template
+// flag and the inference instantiations are untouched by it
+template <int kLP, int kVec, bool kTable, bool kLse>
+__global__ __launch_bounds__(kConvThreads, kTable ? (kLse ? 3 : 4) : 2) void gsm_env_conv_kernel(const ConvParams p) {
+    using V = VecT<kVec>;
+    using T = typename V::T;
+    constexpr int kNPP = kConvThreads / kLP;                 // output rows per pass of the block
+    extern __shared__ float4 conv_smem[];
+    char *sm = (char *)conv_smem;
+    const int E = p.E, HC = p.HC;
+    const ConvLds L = conv_lds(p.epb, E, HC, kTable);
+    float *xs = (float *)(sm + L.xs);
+    int64_t *est = (int64_t *)(sm + L.est);
+    int *ecnt = (int *)(sm + L.ecnt), *ebad = (int *)(sm + L.ebad), *rs = (int *)(sm + L.rs);
+    float *ktab = (float *)(sm + L.tab), *vtab = ktab + p.epb * E * HC;
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * p.epb;                       // grid = ceil(B / epb): b0 < B
+    const int ne = min(p.epb, p.B - b0), n_loc = ne * E;
+
+    conv_stage_envs(p, L, sm, b0, ne, tid);
 
     // the per-node offsets env_csr would give (a failed env repeats its start)
     if (p.row_ptr_out) {
@@ -1020,6 +1037,12 @@ __global__ __launch_bounds__(kConvThreads, kTable ? 4 : 2) void gsm_env_conv_ker
             for (int c = 0; c < kVec; ++c)
                 V::set(r, c, V::get(acc, c) * inv + (p.skip ? V::get(sk, c) : 0.0f));
             *(T *)(p.out + ((int64_t)(b0 + g) * R + i) * HC + ch) = r;
+            // softmax statistics for the backward: each head's first lane; an
+            // empty row stores a finite value that is never read
+            if constexpr (kLse)
+                if (ch % p.C == 0)
+                    p.lse[((int64_t)(b0 + g) * R + i) * (HC / p.C) + ch / p.C] =
+                        den > 0.0f ? mx + logf(den) : 0.0f;
         }
     }
 }
@@ -1027,7 +1050,8 @@ __global__ __launch_bounds__(kConvThreads, kTable ? 4 : 2) void gsm_env_conv_ker
 hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
                            int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
                            const float *w_e, int64_t B, int E, int HC, int C, float scale, bool skip,
-                           int n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status, hipStream_t s) {
+                           int n_rows_out, float *out, float *lse, int64_t *row_ptr_out, int32_t *status,
+                           hipStream_t s) {
     // four channels per lane when every head spans whole lanes and the rows are 16-byte aligned
     const bool vec4 = C % 4 == 0 && HC % 4 == 0 &&
                       ((uintptr_t)out | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
@@ -1053,6 +1077,7 @@ hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, cons
     p.n_rows_out = n_rows_out;
     p.scale = scale;
     p.out = out;
+    p.lse = lse;
     p.row_ptr_out = row_ptr_out;
     p.status = status;
     const bool table = conv_lds(p.epb, E, HC, true).total <= kConvLdsMax;
@@ -1060,10 +1085,12 @@ hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, cons
     if (lds > (size_t)kConvLdsMax) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((B + p.epb - 1) / p.epb);
     (void)hipGetLastError();
-#define GSM_CONV(LP, VEC)                                                                     \
-    do {                                                                                      \
-        if (table) gsm_env_conv_kernel<LP, VEC, true><<<blocks, kConvThreads, lds, s>>>(p);   \
-        else gsm_env_conv_kernel<LP, VEC, false><<<blocks, kConvThreads, lds, s>>>(p);        \
+#define GSM_CONV(LP, VEC)                                                                                       \
+    do {                                                                                                        \
+        if (table && lse) gsm_env_conv_kernel<LP, VEC, true, true><<<blocks, kConvThreads, lds, s>>>(p);        \
+        else if (table) gsm_env_conv_kernel<LP, VEC, true, false><<<blocks, kConvThreads, lds, s>>>(p);         \
+        else if (lse) gsm_env_conv_kernel<LP, VEC, false, true><<<blocks, kConvThreads, lds, s>>>(p);           \
+        else gsm_env_conv_kernel<LP, VEC, false, false><<<blocks, kConvThreads, lds, s>>>(p);                   \
     } while (0)
     if (vec4) {
         switch (lp) {
@@ -1087,6 +1114,462 @@ hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, cons
         }
     }
 #undef GSM_CONV
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Backward of the fused first layer (gsm_env_conv_bwd). node_feat and
+// edge_attr are env data, so the gradients are those of the weights alone:
+// with x_i the node's seven features and a trailing 1, g_i = grad_out of row i
+// (0 for i >= n_rows_out) and dq, dk, dv of the aggregation's backward above,
+//
+//   dW_q[c][f] = sum_i dq_i[c] x_i[f]     dW_skip[c][f] = sum_i g_i[c] x_i[f]
+//   dW_k[c][f] = sum_j dk_j[c] x_j[f]     dW_v[c][f]    = sum_j dv_j[c] x_j[f]
+//   dw_e[c]    = sum_i scale q_i[c] U_i + g_i[c] A_i
+//
+// over every node of every env. The forward's structure: a workgroup holds
+// max(1, 64 / E) envs, staged and checked by conv_stage_envs exactly as the
+// forward stages them (a failed env is edgeless here too: its rows reach
+// dW_skip only), with the k, v table or the recompute form. Per env group:
+//
+//   target pass  the forward's lane mapping over the output rows: q_i, skip_i
+//                recomputed from the LDS row, D_i from g_i and out_i - skip_i,
+//                a_ij = exp(s_ij - lse_i) with s_ij in the forward's operation
+//                order; dq_i in registers; a_ij, ds_ij per (entry, head) ->
+//                work, at the entry's own position in the edge arrays (read
+//                back by this workgroup after a barrier: L2-resident)
+//   source pass  the env graphs are symmetric with ascending columns, so row j
+//                lists exactly the targets i that list j: node j walks its own
+//                row and finds j inside row i, its position = the number of
+//                row i's columns below j, counted by the slot's kLP lanes side
+//                by side over row i's checked range [rs[i], rs[i+1]) (loads
+//                that do not wait for one another, where a binary search's
+//                do); reads a, ds there, recomputes q_i, reads g_i and sums
+//                dk_j, dv_j in registers in ascending i. Every entry's reverse
+//                entry is looked for; a missing one sets GSM_BATCH_ASYMMETRIC
+//                and contributes nothing
+//   weights      after each pass of kNPP rows the lanes' (dq, g) or (dk, dv)
+//                go through an LDS stage; thread (array, channel c) adds
+//                d[c] * x[f] of the staged rows in slot order to its eight
+//                accumulators, which live in registers across the env groups
+//                the workgroup walks (a capped grid, groups in order)
+//
+// A workgroup ends with one partial [3 or 4][HC][8] + [HC]; a second launch
+// sums the partials of each value in index order. No float atomics anywhere:
+// the summation order is fixed by the shape alone, so dw and dw_e are bitwise
+// reproducible.
+
+// grid cap = weight-gradient partials: the workgroups that are resident at once
+// (three a CU at the table form's 168 VGPRs, two at the recompute form's, fewer
+// when their LDS does not fit a CU's 160 KiB) on 256 CUs, so that no workgroup
+// waits for another to end; constants, so the count, hence the summation order,
+// is the same on every device
+constexpr int kConvBwdMaxBlocks = 768;
+constexpr int kConvBwdCus = 256, kConvBwdLdsPerCu = 160 * 1024;
+
+struct ConvBwdParams {
+    ConvParams f;                 // graph, weights, shape, status; f.out, f.lse, f.row_ptr_out unused
+    const float *grad_out, *out, *lse;
+    float *wa, *wds;              // [edge_limit][H]: a_ij, ds_ij at the entry's position
+    float *part;                  // [gridDim.x][nblk*HC*8 + HC]
+    int n_groups, want_dwe;
+};
+
+// the pass stage [2][kConvThreads * vec], then the weight-gradient accumulators [16][2 * HC]
+__host__ __device__ inline int conv_bwd_stage_bytes(int vec, int HC) {
+    return 2 * kConvThreads * vec * 4 + 16 * 2 * HC * 4;
+}
+
+// the rows staged by one pass -> this thread's eight accumulators (in LDS
+// between the passes, stride apart, so that the walks have the registers), in
+// slot order
+template <int kLP, int kVec>
+__device__ __forceinline__ void conv_bwd_accumulate(const float *__restrict__ col, const float *__restrict__ xs,
+                                                    int base, int n_rows, int R, int E, float *__restrict__ racc,
+                                                    int stride) {
+    constexpr int kNPP = kConvThreads / kLP;
+    const int n = min(kNPP, n_rows - base);
+    int g = base / R, i = base - g * R;
+    float acc[8];
+#pragma unroll
+    for (int f = 0; f < 8; ++f) acc[f] = racc[f * stride];
+    for (int s = 0; s < n; ++s) {
+        const float d = col[s * kLP * kVec];
+        const float *x = xs + (g * E + i) * 8;
+        const float4 x0 = *(const float4 *)x, x1 = *(const float4 *)(x + 4);
+        acc[0] += d * x0.x, acc[1] += d * x0.y, acc[2] += d * x0.z, acc[3] += d * x0.w;
+        acc[4] += d * x1.x, acc[5] += d * x1.y, acc[6] += d * x1.z, acc[7] += d;
+        if (++i == R) i = 0, ++g;
+    }
+#pragma unroll
+    for (int f = 0; f < 8; ++f) racc[f * stride] = acc[f];
+}
+
+template <int kLP, int kVec, bool kTable>
+__global__ __launch_bounds__(kConvThreads, kTable ? 3 : 2) void gsm_env_conv_bwd_kernel(const ConvBwdParams bp) {
+    using V = VecT<kVec>;
+    using T = typename V::T;
+    constexpr int kNPP = kConvThreads / kLP;                 // rows per pass of the block
+    extern __shared__ float4 conv_smem[];
+    char *sm = (char *)conv_smem;
+    const ConvParams &p = bp.f;
+    const int E = p.E, HC = p.HC, C = p.C, H = HC / C, R = p.n_rows_out;
+    const ConvLds L = conv_lds(p.epb, E, HC, kTable);
+    float *xs = (float *)(sm + L.xs);
+    int64_t *est = (int64_t *)(sm + L.est);
+    int *ebad = (int *)(sm + L.ebad), *rs = (int *)(sm + L.rs);
+    float *ktab = (float *)(sm + L.tab), *vtab = ktab + p.epb * E * HC;
+    float *stage = (float *)(sm + L.total);                  // [2][kConvThreads * kVec], then the accumulators
+    const int tid = threadIdx.x;
+    const int slot = tid / kLP, sub = tid % kLP, ch = sub * kVec;
+    const bool chon = ch < HC;
+    const int head = chon ? ch / C : 0;
+    const int lanes_per_head = C / kVec;                     // power of two
+    // weight gradients: thread (array ra, channel rc) of the first 2 * HC
+    const bool red = tid < 2 * HC;
+    const int ra = tid >= HC ? 1 : 0, rc = tid - ra * HC;
+    const float *rcol = stage + ra * kConvThreads * kVec + (rc / kVec) * kVec + rc % kVec;
+    // its accumulators [f][tid]: f < 8 the target pass (W_q | W_skip), then the source pass (W_k | W_v);
+    // touched by this thread alone
+    float *racc = stage + 2 * kConvThreads * kVec + tid;
+    if (red)
+        for (int f = 0; f < 16; ++f) racc[f * 2 * HC] = 0.0f;
+    float wq[kVec][8], wk[kVec][8], wv[kVec][8];             // the skip block is fetched where a row needs it
+    conv_load_w<kVec>(p.w, 0, HC, ch, chon, wq);
+    if constexpr (!kTable) {
+        conv_load_w<kVec>(p.w, 1, HC, ch, chon, wk);
+        conv_load_w<kVec>(p.w, 2, HC, ch, chon, wv);
+    }
+    T we, dwe;
+    for (int c = 0; c < kVec; ++c) {
+        V::set(we, c, 0.0f);
+        V::set(dwe, c, 0.0f);
+    }
+    if (chon && p.w_e) we = *(const T *)(p.w_e + ch);
+    int bits = 0;
+
+    for (int grp = blockIdx.x; grp < bp.n_groups; grp += gridDim.x) {
+        const int b0 = grp * p.epb;
+        const int ne = min(p.epb, p.B - b0), n_loc = ne * E;
+        conv_stage_envs(p, L, sm, b0, ne, tid);
+        if constexpr (kTable) {
+            conv_load_w<kVec>(p.w, 1, HC, ch, chon, wk);
+            conv_load_w<kVec>(p.w, 2, HC, ch, chon, wv);
+            if (chon)
+                for (int x = slot; x < n_loc; x += kNPP) {
+                    const float4 x0 = *(const float4 *)(xs + x * 8), x1 = *(const float4 *)(xs + x * 8 + 4);
+                    *(T *)(ktab + x * HC + ch) = conv_project<kVec>(wk, x0, x1);
+                    *(T *)(vtab + x * HC + ch) = conv_project<kVec>(wv, x0, x1);
+                }
+            __syncthreads();
+        }
+
+        // target pass
+        const int n_walk = ne * R;
+        for (int base = 0; base < n_walk; base += kNPP) {    // block-uniform trip count
+            const int idx = base + slot;
+            const bool have = idx < n_walk, live = have && chon;
+            const int id = have ? idx : 0;
+            const int g = id / R, i = id - g * R, gE = g * E;
+            const float4 x0 = *(const float4 *)(xs + (gE + i) * 8), x1 = *(const float4 *)(xs + (gE + i) * 8 + 4);
+            const T qi = conv_project<kVec>(wq, x0, x1);
+            const bool good = have && !ebad[g];
+            const int r0 = good ? rs[g * (E + 1) + i] : 0;
+            const int deg = good ? rs[g * (E + 1) + i + 1] - r0 : 0;
+            const int64_t e0 = est[g] + r0;                  // the row's first entry in the edge arrays
+            const int32_t *colp = p.ecol + e0;
+            const float *attrp = p.edge_attr + e0;
+            const uint32_t bE = (uint32_t)(b0 + g) * (uint32_t)E;
+            const int64_t row = (int64_t)(b0 + g) * R + i;
+            T gi, acc;
+            for (int c = 0; c < kVec; ++c) {
+                V::set(gi, c, 0.0f);
+                V::set(acc, c, 0.0f);
+            }
+            float D = 0.0f, ls = 0.0f;
+            if (live) {
+                gi = *(const T *)(bp.grad_out + row * HC + ch);
+                T om = *(const T *)(bp.out + row * HC + ch);
+                if (p.skip) {
+                    float ws[kVec][8];
+                    conv_load_w<kVec>(p.w, 3, HC, ch, true, ws);
+                    const T sk = conv_project<kVec>(ws, x0, x1);
+                    for (int c = 0; c < kVec; ++c) V::set(om, c, V::get(om, c) - V::get(sk, c));
+                }
+#pragma unroll
+                for (int c = 0; c < kVec; ++c) D += V::get(gi, c) * V::get(om, c);
+                ls = bp.lse[row * H + head];
+            }
+#pragma unroll
+            for (int o = 1; o < kLP; o <<= 1)
+                if (o < lanes_per_head) D += __shfl_xor(D, o);
+            int wdeg = deg;                                  // the wave runs its longest row
+#pragma unroll
+            for (int o = kLP; o < kWave; o <<= 1) wdeg = max(wdeg, __shfl_xor(wdeg, o));
+            float U = 0.0f, A = 0.0f;
+            int32_t jn = (live && deg > 0) ? colp[0] : 0;
+            float wn = (live && deg > 0 && p.w_e) ? attrp[0] : 0.0f;
+            for (int t = 0; t < wdeg; ++t) {
+                const bool on = live && t < deg;
+                const int jl = min(max((int)((uint32_t)jn - bE), 0), E - 1);   // checked by conv_stage_envs; clamped again
+                const float w = wn;
+                if (live && t + 1 < deg) {
+                    jn = colp[t + 1];
+                    if (p.w_e) wn = attrp[t + 1];
+                }
+                T kj, vj;
+                for (int c = 0; c < kVec; ++c) {
+                    V::set(kj, c, 0.0f);
+                    V::set(vj, c, 0.0f);
+                }
+                if (on) {
+                    if constexpr (kTable) {
+                        kj = *(const T *)(ktab + (gE + jl) * HC + ch);
+                        vj = *(const T *)(vtab + (gE + jl) * HC + ch);
+                    } else {
+                        const float4 y0 = *(const float4 *)(xs + (gE + jl) * 8),
+                                     y1 = *(const float4 *)(xs + (gE + jl) * 8 + 4);
+                        kj = conv_project<kVec>(wk, y0, y1);
+                        vj = conv_project<kVec>(wv, y0, y1);
+                    }
+                }
+                float sc = 0.0f, gm = 0.0f;
+#pragma unroll
+                for (int c = 0; c < kVec; ++c) {
+                    sc += V::get(qi, c) * (V::get(kj, c) + w * V::get(we, c));
+                    gm += V::get(gi, c) * (V::get(vj, c) + w * V::get(we, c));
+                }
+#pragma unroll
+                for (int o = 1; o < kLP; o <<= 1)
+                    if (o < lanes_per_head) {
+                        sc += __shfl_xor(sc, o);
+                        gm += __shfl_xor(gm, o);
+                    }
+                sc *= p.scale;
+                const float a = on ? __expf(sc - ls) : 0.0f;
+                const float ds = a * (gm - D);
+#pragma unroll
+                for (int c = 0; c < kVec; ++c)
+                    V::set(acc, c, V::get(acc, c) + ds * (V::get(kj, c) + w * V::get(we, c)));
+                U += w * ds;
+                A += w * a;
+                if (on && ch % C == 0) {
+                    bp.wa[(e0 + t) * H + head] = a;
+                    bp.wds[(e0 + t) * H + head] = ds;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < kVec; ++c) {
+                stage[tid * kVec + c] = live ? V::get(acc, c) * p.scale : 0.0f;
+                stage[(kConvThreads + tid) * kVec + c] = V::get(gi, c);
+                if (live) V::set(dwe, c, V::get(dwe, c) + (p.scale * V::get(qi, c) * U + V::get(gi, c) * A));
+            }
+            __syncthreads();
+            if (red && (ra == 0 || p.skip)) conv_bwd_accumulate<kLP, kVec>(rcol, xs, base, n_walk, R, E, racc, 2 * HC);
+            __syncthreads();
+        }
+        // the barrier above also orders this workgroup's stores to work before the loads below
+
+        // source pass
+        for (int base = 0; base < n_loc; base += kNPP) {     // block-uniform trip count
+            const int idx = base + slot;
+            const bool have = idx < n_loc;
+            const int id = have ? idx : 0;
+            const int g = id / E, j = id - g * E, gE = g * E;
+            const bool good = have && !ebad[g];              // every lane of the slot walks the row
+            const int *rg = rs + g * (E + 1);
+            const int r0 = good ? rg[j] : 0;
+            const int deg = good ? rg[j + 1] - r0 : 0;
+            const int32_t *ecol = p.ecol + est[g];           // the env's columns: positions [0, ecnt[g])
+            const uint32_t bE = (uint32_t)(b0 + g) * (uint32_t)E;
+            const int32_t self = (int32_t)(bE + (uint32_t)j);
+            T ak, av;
+            for (int c = 0; c < kVec; ++c) {
+                V::set(ak, c, 0.0f);
+                V::set(av, c, 0.0f);
+            }
+            int32_t in = deg > 0 ? ecol[r0] : 0;             // next entry's target fetched one iteration ahead
+            for (int t = 0; t < deg; ++t) {
+                const int il = min(max((int)((uint32_t)in - bE), 0), E - 1);   // checked by conv_stage_envs; clamped again
+                if (t + 1 < deg) in = ecol[r0 + t + 1];
+                // j inside row il: the slot's lanes count that row's columns below j and the
+                // hits, every read inside the row's checked range [rg[il], rg[il + 1])
+                const int lo = rg[il], hi = rg[il + 1];
+                int cnt = 0;                                 // columns below j, hits << 16 (a row has < 2^16 entries)
+                for (int x = lo + sub; x < hi; x += kLP) {
+                    const int32_t cx = ecol[x];
+                    cnt += (cx < self ? 1 : 0) + (cx == self ? 1 << 16 : 0);
+                }
+#pragma unroll
+                for (int o = 1; o < kLP; o <<= 1) cnt += __shfl_xor(cnt, o);
+                if (!(cnt >> 16)) {
+                    bits |= GSM_BATCH_ASYMMETRIC;
+                    continue;
+                }
+                if (il >= R || !chon) continue;              // not an output row: g_i = 0
+                const int64_t e = (est[g] + lo + (cnt & 0xffff)) * H + head;
+                const float a = bp.wa[e], ds = bp.wds[e];
+                const float4 y0 = *(const float4 *)(xs + (gE + il) * 8), y1 = *(const float4 *)(xs + (gE + il) * 8 + 4);
+                const T qi = conv_project<kVec>(wq, y0, y1);
+                const T gi = *(const T *)(bp.grad_out + ((int64_t)(b0 + g) * R + il) * HC + ch);
+#pragma unroll
+                for (int c = 0; c < kVec; ++c) {
+                    V::set(ak, c, V::get(ak, c) + ds * V::get(qi, c));
+                    V::set(av, c, V::get(av, c) + a * V::get(gi, c));
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < kVec; ++c) {
+                stage[tid * kVec + c] = V::get(ak, c) * p.scale;
+                stage[(kConvThreads + tid) * kVec + c] = V::get(av, c);
+            }
+            __syncthreads();
+            if (red) conv_bwd_accumulate<kLP, kVec>(rcol, xs, base, n_loc, E, E, racc + 16 * HC, 2 * HC);
+            __syncthreads();
+        }
+    }
+    if (bits) atomicOr(p.status, bits);
+
+    // this workgroup's partial: [nblk][HC][8], then dw_e [HC] summed in slot order
+    const int nblk = p.skip ? 4 : 3;
+    float *part = bp.part + (int64_t)blockIdx.x * (nblk * HC * 8 + HC);
+    if (red) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f) {
+            if (ra == 0 || p.skip) part[((ra ? 3 : 0) * HC + rc) * 8 + f] = racc[f * 2 * HC];
+            part[((1 + ra) * HC + rc) * 8 + f] = racc[(8 + f) * 2 * HC];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kVec; ++c) stage[tid * kVec + c] = V::get(dwe, c);
+    __syncthreads();
+    if (tid < HC) {
+        float sum = 0.0f;
+        if (bp.want_dwe)
+            for (int s = 0; s < kNPP; ++s) sum += stage[(s * kLP + tid / kVec) * kVec + tid % kVec];
+        part[nblk * HC * 8 + tid] = sum;
+    }
+}
+
+// partial sums -> dw, dw_e: a workgroup takes 64 of the values; row group r
+// sums partials r, r+R, .. in order, then the value's thread sums the R row
+// groups in order (gsm_attn_bwd_dwe_kernel's scheme)
+__global__ __launch_bounds__(64 * kBwdSumRows) void gsm_env_conv_bwd_sum_kernel(const float *__restrict__ part,
+                                                                                int n_part, int n_w, int n_e,
+                                                                                float *__restrict__ dw,
+                                                                                float *__restrict__ dw_e) {
+    __shared__ float red[kBwdSumRows][64];
+    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane, W = n_w + n_e;
+    float sum = 0.0f;
+    if (c < W)
+        for (int b = r; b < n_part; b += 8 * kBwdSumRows) {
+            float x[8];                                    // eight loads in flight, added in order
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int bu = b + u * kBwdSumRows;
+                x[u] = bu < n_part ? part[(int64_t)bu * W + c] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sum += x[u];
+        }
+    red[r][lane] = sum;
+    __syncthreads();
+    if (r == 0 && c < W) {
+        float tot = 0.0f;
+        for (int i = 0; i < kBwdSumRows; ++i) tot += red[i][lane];
+        if (c < n_w) dw[c] = tot;
+        else if (dw_e) dw_e[c - n_w] = tot;
+    }
+}
+
+int64_t env_conv_backward_work_floats(int64_t edge_limit, int heads, int HC, bool skip) {
+    return 2 * edge_limit * heads + (int64_t)kConvBwdMaxBlocks * ((skip ? 4 : 3) * HC * 8 + HC);
+}
+
+hipError_t launch_env_conv_backward(const float *grad_out, const float *node_feat, const int64_t *edge_ptr,
+                                    const int32_t *edge_index, int64_t edge_row_stride, const float *edge_attr,
+                                    int64_t edge_limit, const float *w, const float *w_e, const float *out,
+                                    const float *lse, int64_t B, int E, int HC, int C, float scale, bool skip,
+                                    int n_rows_out, float *work, float *dw, float *dw_e, int32_t *status,
+                                    hipStream_t s) {
+    // the forward's choice of lanes, so that s_ij is formed in the forward's order
+    const bool vec4 = C % 4 == 0 && HC % 4 == 0 &&
+                      ((uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
+    const int vec = vec4 ? 4 : 1;
+    int lp = 1;
+    while (lp * vec < HC) lp <<= 1;
+    if (lp > kWave) return hipErrorInvalidValue;
+    const int H = HC / C, nblk = skip ? 4 : 3;
+    ConvBwdParams bp;
+    ConvParams &p = bp.f;
+    p.node_feat = node_feat;
+    p.edge_ptr = edge_ptr;
+    p.erow = edge_index;
+    p.ecol = edge_index ? edge_index + edge_row_stride : nullptr;
+    p.edge_attr = edge_attr;
+    p.edge_limit = edge_limit;
+    p.w = w;
+    p.w_e = w_e;
+    p.B = (int)B;
+    p.E = E;
+    p.epb = E >= 64 ? 1 : 64 / E;
+    p.HC = HC;
+    p.C = C;
+    p.skip = skip;
+    p.n_rows_out = n_rows_out;
+    p.scale = scale;
+    p.out = nullptr;
+    p.lse = nullptr;
+    p.row_ptr_out = nullptr;
+    p.status = status;
+    bp.grad_out = grad_out;
+    bp.out = out;
+    bp.lse = lse;
+    bp.wa = work;
+    bp.wds = work + edge_limit * H;
+    bp.part = work + 2 * edge_limit * H;
+    bp.n_groups = (int)((B + p.epb - 1) / p.epb);
+    bp.want_dwe = w_e && dw_e;
+    // the table form when it fits with the stage, as launch_env_conv decides it
+    const int stage = conv_bwd_stage_bytes(vec, HC);
+    const bool table = conv_lds(p.epb, E, HC, true).total + stage <= kConvLdsMax;
+    const size_t lds = (size_t)(conv_lds(p.epb, E, HC, table).total + stage);
+    if (lds > (size_t)kConvLdsMax) return hipErrorInvalidValue;
+    const int per_cu = min(table ? 3 : 2, max(1, kConvBwdLdsPerCu / (int)lds));
+    const int cap = min(kConvBwdMaxBlocks, kConvBwdCus * per_cu);
+    const unsigned blocks = (unsigned)(bp.n_groups < cap ? bp.n_groups : cap);
+    (void)hipGetLastError();
+#define GSM_CONV_BWD(LP, VEC)                                                                     \
+    do {                                                                                          \
+        if (table) gsm_env_conv_bwd_kernel<LP, VEC, true><<<blocks, kConvThreads, lds, s>>>(bp);  \
+        else gsm_env_conv_bwd_kernel<LP, VEC, false><<<blocks, kConvThreads, lds, s>>>(bp);       \
+    } while (0)
+    if (vec4) {
+        switch (lp) {
+            case 1: GSM_CONV_BWD(1, 4); break;
+            case 2: GSM_CONV_BWD(2, 4); break;
+            case 4: GSM_CONV_BWD(4, 4); break;
+            case 8: GSM_CONV_BWD(8, 4); break;
+            case 16: GSM_CONV_BWD(16, 4); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (lp) {
+            case 1: GSM_CONV_BWD(1, 1); break;
+            case 2: GSM_CONV_BWD(2, 1); break;
+            case 4: GSM_CONV_BWD(4, 1); break;
+            case 8: GSM_CONV_BWD(8, 1); break;
+            case 16: GSM_CONV_BWD(16, 1); break;
+            case 32: GSM_CONV_BWD(32, 1); break;
+            case 64: GSM_CONV_BWD(64, 1); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
+#undef GSM_CONV_BWD
+    const int n_w = nblk * HC * 8;
+    gsm_env_conv_bwd_sum_kernel<<<(unsigned)((n_w + HC + 63) / 64), 64 * kBwdSumRows, 0, s>>>(
+        bp.part, (int)blocks, n_w, HC, dw, dw_e);
     return hipGetLastError();
 }
 

@@ -294,7 +294,17 @@ hipError_t launch_graph_batch_gather(const float *node_feat, const int32_t *edge
 hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
                            int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
                            const float *w_e, int64_t B, int E, int HC, int C, float scale, bool skip,
-                           int n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status, hipStream_t s);
+                           int n_rows_out, float *out, float *lse, int64_t *row_ptr_out, int32_t *status,
+                           hipStream_t s);
+// floats of workspace launch_env_conv_backward needs: a_ij and ds_ij per
+// (entry position, head), then one weight-gradient partial per workgroup
+int64_t env_conv_backward_work_floats(int64_t edge_limit, int heads, int HC, bool skip);
+hipError_t launch_env_conv_backward(const float *grad_out, const float *node_feat, const int64_t *edge_ptr,
+                                    const int32_t *edge_index, int64_t edge_row_stride, const float *edge_attr,
+                                    int64_t edge_limit, const float *w, const float *w_e, const float *out,
+                                    const float *lse, int64_t B, int E, int HC, int C, float scale, bool skip,
+                                    int n_rows_out, float *work, float *dw, float *dw_e, int32_t *status,
+                                    hipStream_t s);
 hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
                       float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,

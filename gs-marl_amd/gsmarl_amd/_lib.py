@@ -110,6 +110,12 @@ SIGNATURES = {
                                          C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "gsm_env_conv": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32,
                                C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "gsm_env_conv_fwd": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "gsm_env_conv_backward_work_floats": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.POINTER(C.c_int64)]),
+    "gsm_env_conv_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "gsm_gae": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "gsm_render": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

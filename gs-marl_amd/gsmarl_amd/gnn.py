@@ -27,7 +27,12 @@ restates that layer:
   graph of ``GpuBatchEnv.step`` / ``GraphRolloutBuffer.slot`` (``gsm_env_conv``):
   no ``env_csr``, no [n, HC] tensors; ``TransformerConv.forward_env`` takes it on
   the inference path and ``env_conv_ref`` (plain torch, differentiable)
-  elsewhere.
+  elsewhere;
+* ``env_conv_autograd`` is that layer with gradients for its weights
+  (``gsm_env_conv_fwd`` / ``gsm_env_conv_bwd``: the backward recomputes the
+  projections on chip too, so what leaves it is ``dw`` and ``dw_e``, a few KB;
+  ``env_conv_bwd_ref`` is its torch restatement), which
+  ``TransformerConv(kernel_backward=True).forward_env`` trains on.
 
 Graph format: CSR over targets (``row_ptr`` [n+1] int64, ``col`` int32
 sources, ``edge_w`` per CSR entry). The env graphs are symmetric (every radius
@@ -336,23 +341,48 @@ def env_conv_ref(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows
     return (out, ptr) if row_ptr else out
 
 
-def env_conv(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out, skip, row_ptr=False, check=True):
-    """One TransformerConv layer (in_channels 7, edge_dim 1 or None, concat) on
-    an env-form graph in one HIP launch (gsm_env_conv in include/gsm.h; no
-    autograd). ``node_feat`` f32 [B, E, 7]; ``edge_ptr`` int64 [B+1];
-    ``edge_index`` int32 [2, cap] or its ``[:, :total]`` view (the row stride
-    is taken from the tensor, the entry bound is ``shape[1]``); ``edge_attr``
-    f32 with at least that many entries; ``w``, ``w_e`` from
-    ``pack_conv_params``; ``rows_out``: E for every row, N for the agents'.
-    Returns ``out`` [B, rows_out, HC], then ``row_ptr`` int64 [B*E+1] (the
-    offsets ``env_csr`` gives) when asked for. With ``check`` one read of the
-    kernel's status raises ValueError for an env whose entries run past the
-    bound (a truncated rollout slot) and RuntimeError for corrupt offsets or
-    ids; without it the status (device int32 [1], GSM_BATCH_* bits) is
-    returned last and such envs are edgeless."""
+def env_conv_bwd_ref(grad_out, node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out, skip,
+                     node_grads=False):
+    """The weight gradients of ``env_conv_ref`` written out (plain torch, any
+    dtype and device): the restatement ``gsm_env_conv_bwd`` is written against.
+    ``grad_out`` [B, rows_out, HC]; the rows past ``rows_out`` have ``g_i =
+    0``. With ``x_i`` the node's features and a trailing 1, and ``dq, dk, dv``
+    of ``attn_aggregate_bwd_ref`` on ``env_csr`` of the graph::
+
+        dW_q[c][f]    = sum_i dq_i[c] x_i[f]      dW_k[c][f] = sum_j dk_j[c] x_j[f]
+        dW_skip[c][f] = sum_i g_i[c]  x_i[f]      dW_v[c][f] = sum_j dv_j[c] x_j[f]
+
+    over every node of every env. Returns ``(dw, dw_e)``: ``dw`` [3 or 4, HC,
+    F+1] in the layout of ``pack_conv_params`` (the last column the bias
+    gradient), ``dw_e`` [HC] or None without ``w_e``; with ``node_grads`` also
+    ``(dq, dk, dv, g)``, each [B*E, HC]."""
+    B, E, F = node_feat.shape
+    n = B * E
+    if w.shape[0] != (4 if skip else 3) or w.shape[2] != F + 1:
+        raise ValueError("w: [4 if skip else 3, heads*channels, in_channels+1]")
+    HC = w.shape[1]
+    total = _env_graph_total(edge_ptr, edge_index)
+    ei = edge_index[:, :total]
+    ptr = env_csr(ei, n)
+    x = node_feat.reshape(n, F)
+    q, k, v = (x @ w[i, :, :F].t() + w[i, :, F] for i in range(3))
+    sk = x @ w[3, :, :F].t() + w[3, :, F] if skip else None
+    ew = edge_attr.reshape(-1)[:total] if w_e is not None else None
+    g = torch.zeros(B, E, HC, dtype=x.dtype, device=x.device)
+    g[:, :rows_out] = grad_out
+    g = g.view(n, HC)
+    dq, dk, dv, _, dw_e, _ = attn_aggregate_bwd_ref(g, q, k, v, ptr, ei[1], ew, w_e, sk, heads)
+    x1 = torch.cat([x, torch.ones(n, 1, dtype=x.dtype, device=x.device)], 1)
+    dw = torch.stack([d.t() @ x1 for d in (dq, dk, dv) + ((g,) if skip else ())])
+    return (dw, dw_e, (dq, dk, dv, g)) if node_grads else (dw, dw_e)
+
+
+def _env_conv_args(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, skip, what):
+    """The argument checks of ``env_conv`` / ``env_conv_autograd``. Returns
+    ``(edge_attr flattened, w_e contiguous, entry bound, row stride, HC)``."""
     dev = node_feat.device
     if dev.type != "cuda":
-        raise _lib.GsmError("env_conv needs a ROCm GPU; use env_conv_ref on the CPU")
+        raise _lib.GsmError(f"{what} needs a ROCm GPU; use env_conv_ref on the CPU")
     if node_feat.dim() != 3 or node_feat.shape[2] != 7:
         raise ValueError("node_feat: [B, E, 7]")
     B, E, _ = node_feat.shape
@@ -376,13 +406,47 @@ def env_conv(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out
         w_e = w_e.contiguous()
         if w_e.dtype != torch.float32 or w_e.device != dev or w_e.numel() != HC:
             raise ValueError(f"w_e: float32 [heads*channels] on {dev}")
+    stride = int(edge_index.stride(0)) if limit else 0
+    return edge_attr, w_e, limit, stride, HC
+
+
+def _raise_env_status(st, limit, what):
+    if st & _lib.BATCH_TRUNCATED:
+        raise ValueError(f"{what}: an env's entries run past the {limit} stored (a truncated rollout slot); "
+                         "size the buffer with a larger edge capacity")
+    if st:
+        msgs = [m for bit, m in ((_lib.BATCH_BAD_OFFSETS, "an env's edge offsets are not 0 <= start <= end"),
+                                 (_lib.BATCH_OUT_OF_ENV, "an entry's node id lies outside its env or its rows "
+                                                         "do not ascend"),
+                                 (_lib.BATCH_ASYMMETRIC, "an entry's reverse entry is missing (the backward needs "
+                                                         "a symmetric graph)")) if st & bit]
+        raise RuntimeError(f"{what}: the graph is invalid (status {st}): " + "; ".join(msgs))
+
+
+def env_conv(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out, skip, row_ptr=False, check=True):
+    """One TransformerConv layer (in_channels 7, edge_dim 1 or None, concat) on
+    an env-form graph in one HIP launch (gsm_env_conv in include/gsm.h; no
+    autograd). ``node_feat`` f32 [B, E, 7]; ``edge_ptr`` int64 [B+1];
+    ``edge_index`` int32 [2, cap] or its ``[:, :total]`` view (the row stride
+    is taken from the tensor, the entry bound is ``shape[1]``); ``edge_attr``
+    f32 with at least that many entries; ``w``, ``w_e`` from
+    ``pack_conv_params``; ``rows_out``: E for every row, N for the agents'.
+    Returns ``out`` [B, rows_out, HC], then ``row_ptr`` int64 [B*E+1] (the
+    offsets ``env_csr`` gives) when asked for. With ``check`` one read of the
+    kernel's status raises ValueError for an env whose entries run past the
+    bound (a truncated rollout slot) and RuntimeError for corrupt offsets or
+    ids; without it the status (device int32 [1], GSM_BATCH_* bits) is
+    returned last and such envs are edgeless."""
+    edge_attr, w_e, limit, stride, HC = _env_conv_args(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, skip,
+                                                       "env_conv")
+    dev = node_feat.device
+    B, E, _ = node_feat.shape
     Cc = HC // heads
     lib = _lib.load()
     out = torch.empty(B, int(rows_out), HC, dtype=torch.float32, device=dev)
     ptr = torch.empty(B * E + 1, dtype=torch.int64, device=dev) if row_ptr else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    stride = int(edge_index.stride(0)) if limit else 0
     rc = lib.gsm_env_conv(_ptr(node_feat) if B else None, _ptr(edge_ptr), _ptr(edge_index) if limit else None, stride,
                           _ptr(edge_attr) if limit else None, limit, _ptr(w), _ptr(w_e), int(B), int(E), int(heads),
                           int(Cc), 1.0 / math.sqrt(Cc), _lib.CONV_SKIP if skip else 0, int(rows_out), _ptr(out),
@@ -390,17 +454,88 @@ def env_conv(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out
     _lib.check(lib, rc, None, "gsm_env_conv")
     res = (out,) + ((ptr,) if row_ptr else ())
     if check:
-        st = int(status.item())
-        if st & _lib.BATCH_TRUNCATED:
-            raise ValueError(f"env_conv: an env's entries run past the {limit} stored (a truncated rollout slot); "
-                             "size the buffer with a larger edge capacity")
-        if st:
-            what = [m for bit, m in ((_lib.BATCH_BAD_OFFSETS, "an env's edge offsets are not 0 <= start <= end"),
-                                     (_lib.BATCH_OUT_OF_ENV, "an entry's node id lies outside its env or its rows "
-                                                             "do not ascend")) if st & bit]
-            raise RuntimeError(f"env_conv: the graph is invalid (status {st}): " + "; ".join(what))
+        _raise_env_status(int(status.item()), limit, "env_conv")
     else:
         res = res + (status,)
+    return res[0] if len(res) == 1 else res
+
+
+class _EnvConvFn(torch.autograd.Function):
+    """gsm_env_conv_fwd / gsm_env_conv_bwd (include/gsm.h)."""
+
+    @staticmethod
+    def forward(ctx, w, w_e, node_feat, edge_ptr, edge_index, edge_attr, heads, rows_out, skip, want_ptr, check):
+        edge_attr, w_e, limit, stride, HC = _env_conv_args(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads,
+                                                           skip, "env_conv_autograd")
+        dev = node_feat.device
+        B, E, _ = node_feat.shape
+        Cc = HC // heads
+        lib = _lib.load()
+        out = torch.empty(B, rows_out, HC, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, rows_out, heads, dtype=torch.float32, device=dev)
+        ptr = torch.empty(B * E + 1, dtype=torch.int64, device=dev) if want_ptr else None
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib.gsm_env_conv_fwd(_ptr(node_feat) if B else None, _ptr(edge_ptr), _ptr(edge_index) if limit else None,
+                                  stride, _ptr(edge_attr) if limit else None, limit, _ptr(w), _ptr(w_e), int(B),
+                                  int(E), int(heads), int(Cc), 1.0 / math.sqrt(Cc), _lib.CONV_SKIP if skip else 0,
+                                  rows_out, _ptr(out), _ptr(lse), _ptr(ptr), _ptr(status), stream)
+        _lib.check(lib, rc, None, "gsm_env_conv_fwd")
+        if check:
+            _raise_env_status(int(status.item()), limit, "env_conv_autograd")
+        ctx.save_for_backward(w, w_e, node_feat, edge_ptr, edge_index, edge_attr, out, lse, status)
+        ctx.args = (heads, rows_out, skip, check, limit, stride)
+        ctx.mark_non_differentiable(status, *((ptr,) if want_ptr else ()))
+        return out, ptr, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_ptr, _grad_status):
+        w, w_e, node_feat, edge_ptr, edge_index, edge_attr, out, lse, status = ctx.saved_tensors
+        heads, rows_out, skip, check, limit, stride = ctx.args
+        dev = node_feat.device
+        B, E, _ = node_feat.shape
+        HC = int(w.shape[1])
+        Cc = HC // heads
+        lib = _lib.load()
+        g = grad_out.to(torch.float32).contiguous()
+        flags = _lib.CONV_SKIP if skip else 0
+        nf = C.c_int64()
+        _lib.check(lib, lib.gsm_env_conv_backward_work_floats(int(B), int(E), limit, int(heads), int(Cc), flags,
+                                                              C.byref(nf)), None, "gsm_env_conv_backward_work_floats")
+        work = torch.empty(nf.value, dtype=torch.float32, device=dev)
+        dw = torch.empty_like(w)
+        dw_e = torch.empty_like(w_e) if (w_e is not None and ctx.needs_input_grad[1]) else None
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib.gsm_env_conv_bwd(_ptr(g) if B else None, _ptr(node_feat) if B else None, _ptr(edge_ptr),
+                                  _ptr(edge_index) if limit else None, stride, _ptr(edge_attr) if limit else None,
+                                  limit, _ptr(w), _ptr(w_e), _ptr(out) if B else None, _ptr(lse) if B else None,
+                                  int(B), int(E), int(heads), int(Cc), 1.0 / math.sqrt(Cc), flags, rows_out,
+                                  _ptr(work), _ptr(dw), _ptr(dw_e), _ptr(status), stream)
+        _lib.check(lib, rc, None, "gsm_env_conv_bwd")
+        if check:
+            _raise_env_status(int(status.item()), limit, "env_conv_autograd (backward)")
+        return (dw if ctx.needs_input_grad[0] else None, dw_e) + (None,) * 9
+
+
+def env_conv_autograd(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out, skip, row_ptr=False,
+                      check=True):
+    """``env_conv`` with gradients for ``w`` and ``w_e``: forward and backward
+    both on the HIP kernels (gsm_env_conv_fwd / gsm_env_conv_bwd in
+    include/gsm.h), so neither direction forms an [n, HC] tensor. The
+    arguments and the results are ``env_conv``'s; ``node_feat`` and
+    ``edge_attr`` are env data and get no gradient (a call that wants one takes
+    ``env_conv_ref``); no double backward. The backward checks the graph again
+    (it trusts no forward) and, relying on the env graph's symmetry, also
+    reports an entry whose reverse entry is missing. With ``check`` the status
+    is read once in the forward and once in the backward, each raising as
+    ``env_conv`` does; without it the status tensor is returned last, and the
+    backward ORs its bits into that same tensor (no read)."""
+    if node_feat.requires_grad or edge_attr.requires_grad:
+        raise ValueError("env_conv_autograd: no gradients for node_feat or edge_attr; use env_conv_ref")
+    out, ptr, status = _EnvConvFn.apply(w, w_e, node_feat, edge_ptr, edge_index, edge_attr, int(heads), int(rows_out),
+                                        bool(skip), bool(row_ptr), bool(check))
+    res = (out,) + ((ptr,) if row_ptr else ()) + (() if check else (status,))
     return res[0] if len(res) == 1 else res
 
 
@@ -413,7 +548,10 @@ class TransformerConv(torch.nn.Module):
     too; ``forward(..., transpose=csr_transpose(row_ptr, col))`` reuses the
     transposed graph across calls. The default keeps the torch formulation.
     ``forward_env`` is the layer on an env-form graph (what the env returns, or
-    a rollout-buffer slot), fused into one launch where ``env_conv`` applies."""
+    a rollout-buffer slot), fused into one launch where ``env_conv`` applies;
+    with ``kernel_backward=True`` it trains on the fused kernels as well
+    (``env_conv_autograd``: gradients for the parameters, none for the env
+    data)."""
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
                  edge_dim: Optional[int] = 1, root_weight: bool = True, use_kernel: bool = True,
@@ -452,17 +590,30 @@ class TransformerConv(torch.nn.Module):
                 out = out + self.lin_skip(x)
         return out
 
-    def _env_kernel_ok(self, node_feat, edge_attr):
+    def _env_kernel_shapes(self, node_feat):
         if not (self.use_kernel and self.concat and node_feat.is_cuda and node_feat.dtype == torch.float32):
             return False
         if self.lin_query.in_features != 7 or (self.lin_edge is not None and self.lin_edge.in_features != 1):
             return False
-        if torch.is_grad_enabled() and (node_feat.requires_grad or edge_attr.requires_grad or
-                                        any(p.requires_grad for p in self.parameters())):
-            return False
         B, E, _ = node_feat.shape
         Cc, HC = self.out_channels, self.heads * self.out_channels
         return Cc & (Cc - 1) == 0 and HC <= 64 and 1 <= E <= _lib.CONV_MAX_ENTITIES and B * E < 2 ** 31
+
+    def _env_kernel_ok(self, node_feat, edge_attr):
+        if torch.is_grad_enabled() and (node_feat.requires_grad or edge_attr.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
+            return False
+        return self._env_kernel_shapes(node_feat)
+
+    def _env_kernel_grad_ok(self, node_feat, edge_attr):
+        """The training path of ``forward_env`` on the kernels: opted in, a
+        parameter wants a gradient and the env data does not."""
+        if not (self.kernel_backward and torch.is_grad_enabled()) or node_feat.requires_grad or edge_attr.requires_grad:
+            return False
+        params = list(self.parameters())
+        if not any(p.requires_grad for p in params) or any(p.dtype != torch.float32 for p in params):
+            return False
+        return self._env_kernel_shapes(node_feat)
 
     def _packed(self):
         """``pack_conv_params`` of the current parameter values, packed again
@@ -484,8 +635,12 @@ class TransformerConv(torch.nn.Module):
         ``env_csr``, for a further layer on ``forward``. One HIP launch
         (``env_conv``) when the tensors are on the GPU, no gradient is wanted,
         ``use_kernel``, ``concat``, 7 input features, edge_dim 1 or None and the
-        kernel's shape limits hold; the differentiable torch formulation
-        (``env_conv_ref``) otherwise."""
+        kernel's shape limits hold. Under those same conditions, with
+        ``kernel_backward`` set, a parameter that wants a gradient and env data
+        (``node_feat``, ``edge_attr``) that wants none, the training path runs on
+        the kernels too (``env_conv_autograd``: the fused forward with its
+        softmax statistics and the fused backward, the status read once in each).
+        The differentiable torch formulation (``env_conv_ref``) otherwise."""
         nf, ei, ea = graph["node_feat"], graph["edge_index"], graph["edge_attr"]
         B, E, F = nf.shape
         if rows == "all":
@@ -500,6 +655,10 @@ class TransformerConv(torch.nn.Module):
             w, w_e = self._packed()
             return env_conv(nf.contiguous(), graph["edge_ptr"], ei, ea, w, w_e, self.heads, R,
                             self.lin_skip is not None, row_ptr=row_ptr)
+        if self._env_kernel_grad_ok(nf, ea):
+            w, w_e = pack_conv_params(self)                  # differentiable: autograd splits dw onto the parameters
+            return env_conv_autograd(nf.contiguous(), graph["edge_ptr"], ei, ea, w, w_e, self.heads, R,
+                                     self.lin_skip is not None, row_ptr=row_ptr)
         if self.concat:
             w, w_e = pack_conv_params(self)
             return env_conv_ref(nf, graph["edge_ptr"], ei, ea, w, w_e, self.heads, R, self.lin_skip is not None,

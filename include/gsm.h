@@ -480,6 +480,59 @@ int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t 
                  const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels, float scale,
                  int32_t flags, int32_t n_rows_out, float *out, int64_t *row_ptr_out, int32_t *status,
                  void *stream);
+/* The same launch and the same `out`, bit for bit, and the row softmax
+ * statistics the backward needs: lse f32 [n_envs][n_rows_out][heads], the
+ * row's max_j s_ij + log(sum_j exp(s_ij - max)); an empty row, or a row of an
+ * env treated as edgeless, stores 0, which is never read. */
+int gsm_env_conv_fwd(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
+                     int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit, const float *w,
+                     const float *w_e, int64_t n_envs, int32_t n_entities, int32_t heads, int32_t channels,
+                     float scale, int32_t flags, int32_t n_rows_out, float *out, float *lse, int64_t *row_ptr_out,
+                     int32_t *status, void *stream);
+
+/* Gradients of gsm_env_conv with respect to its weights (node_feat and
+ * edge_attr are env data and get none). grad_out f32
+ * [n_envs][n_rows_out][heads*channels]; out, lse: what gsm_env_conv_fwd wrote
+ * for the same inputs; the graph arguments, w, w_e, the shape, scale, flags
+ * and n_rows_out as in the forward. With g_i = grad_out of row i (0 for the
+ * rows i >= n_rows_out), x_i the node's seven features and a trailing 1, and
+ * the formulas of gsm_attn_aggregate_bwd over an env's entries (m_ij = v_j +
+ * e_ij, a_ij = exp(s_ij - lse_i), s_ij in the forward's operation order):
+ *   D_i[h]   = <g_i[h], out_i[h] - skip_i[h]>
+ *   ds_ij[h] = a_ij[h] * (<g_i[h], m_ij[h]> - D_i[h])
+ *   dq_i[h]  = scale * sum_j ds_ij[h] (k_j[h] + e_ij[h])
+ *   dk_j[h]  = scale * sum_{i: j in row i} ds_ij[h] q_i[h]
+ *   dv_j[h]  =         sum_{i: j in row i} a_ij[h]  g_i[h]
+ *   dW_q[c][f]    = sum_i dq_i[c] x_i[f]     dW_k[c][f] = sum_j dk_j[c] x_j[f]
+ *   dW_skip[c][f] = sum_i g_i[c]  x_i[f]     dW_v[c][f] = sum_j dv_j[c] x_j[f]
+ *   dw_e[c]       = sum_ij edge_attr[ij] (scale * ds_ij[h(c)] q_i[c] + a_ij[h(c)] g_i[c])
+ * the sums over every node of every env (a padding row of a ragged batch has
+ * zero features and reaches the bias column only). dw f32 [3 or 4][heads*
+ * channels][8] in the layout of w (column 7 the bias gradient); dw_e f32
+ * [heads*channels] or NULL (not wanted; it needs w_e). work: device f32,
+ * gsm_env_conv_backward_work_floats of them (a_ij and ds_ij per entry position
+ * and head, and one partial per workgroup).
+ * The backward trusts no forward: every edge_ptr pair, every id and the row
+ * order are checked again exactly as gsm_env_conv checks them, into status
+ * (the same GSM_BATCH_* bits), and an env that fails is edgeless here as it
+ * was there: its rows reach dW_skip only, so the result is the gradient of
+ * what the forward computed. The sums over the rows that contain j use the
+ * env graph's symmetry (columns ascending without duplicates inside a row, so
+ * row j lists exactly the targets that list j): node j walks its own row and
+ * finds itself inside row i by counting the columns below j over that row's
+ * checked range, never outside it (no symmetry is needed by the forward).
+ * Every entry's reverse entry is looked for; a missing one sets
+ * GSM_BATCH_ASYMMETRIC and contributes nothing. No float atomics; the
+ * summation order depends on the shape alone, so dw and dw_e are bitwise
+ * reproducible. The forward's shape limits (GSM_EINVAL); with n_envs == 0 the
+ * gradients are zeros. Stateless; asynchronous on `stream`. */
+int gsm_env_conv_backward_work_floats(int64_t n_envs, int32_t n_entities, int64_t edge_limit, int32_t heads,
+                                      int32_t channels, int32_t flags, int64_t *n_floats);
+int gsm_env_conv_bwd(const float *grad_out, const float *node_feat, const int64_t *edge_ptr,
+                     const int32_t *edge_index, int64_t edge_row_stride, const float *edge_attr, int64_t edge_limit,
+                     const float *w, const float *w_e, const float *out, const float *lse, int64_t n_envs,
+                     int32_t n_entities, int32_t heads, int32_t channels, float scale, int32_t flags,
+                     int32_t n_rows_out, float *work, float *dw, float *dw_e, int32_t *status, void *stream);
 
 /* GAE returns of a stored episode of T = n_steps actions in one launch, with
  * BN = [n_envs][n_agents]: reward f32 [T]BN (entry t: the reward of action t),
