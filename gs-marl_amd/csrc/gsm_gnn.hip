@@ -185,6 +185,7 @@ hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v,
 //
 //   D_i[h]   = <g_i[h], out_i[h] - skip_i[h]>       (= sum_j a_ij <g_i[h], m_ij[h]>)
 //   ds_ij[h] = a_ij[h] * (<g_i[h], m_ij[h]> - D_i[h])
+//            = a_ij[h] * <g_i[h], m_ij[h] - (out_i[h] - skip_i[h])>   (the form evaluated)
 //   dq_i[h]  = scale * sum_j ds_ij[h] (k_j[h] + e_ij[h])
 //   dk_j[h]  = scale * sum_{i: j in row i} ds_ij[h] q_i[h]
 //   dv_j[h]  =         sum_{i: j in row i} a_ij[h]  g_i[h]
@@ -203,7 +204,7 @@ hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v,
 // its nodes in a fixed order (registers across its node groups, then LDS) to
 // one partial, and a one-block launch sums the partials in index order.
 
-// target-kernel grid cap = dw_e partial rows: 5 blocks (its occupancy at 96
+// target-kernel grid cap = dw_e partial rows: 5 blocks (its occupancy at 93
 // VGPRs) on each of the 256 CUs, so every block is resident from the start and
 // the count, hence the summation order, is the same on every device
 constexpr int kBwdMaxBlocks = 1280;
@@ -241,22 +242,24 @@ __global__ __launch_bounds__(256) void gsm_attn_bwd_target_kernel(
             V::set(gi, i, 0.0f);
             V::set(acc, i, 0.0f);
         }
-        float D = 0.0f, ls = 0.0f;
+        // gm_ij - D_i = <g_i, m_ij - (out_i - skip_i)>, formed per channel before the
+        // dot product: where one entry dominates the row, m_ij is out_i - skip_i
+        // to a few bits, the difference is small and so is its rounding, which dq
+        // multiplies by k_j; subtracting two separately rounded dot products
+        // would leave their full rounding there
+        T om;
+        for (int i = 0; i < kVec; ++i) V::set(om, i, 0.0f);
+        float ls = 0.0f;
         if (live) {
             qi = *(const T *)(q + nd * HC + ch);
             gi = *(const T *)(g + nd * HC + ch);
-            T om = *(const T *)(out + nd * HC + ch);
+            om = *(const T *)(out + nd * HC + ch);
             if (skip) {
                 const T sk = *(const T *)(skip + nd * HC + ch);
                 for (int i = 0; i < kVec; ++i) V::set(om, i, V::get(om, i) - V::get(sk, i));
             }
-#pragma unroll
-            for (int i = 0; i < kVec; ++i) D += V::get(gi, i) * V::get(om, i);
             ls = lse[nd * H + head];
         }
-#pragma unroll
-        for (int o = 1; o < kLP; o <<= 1)
-            if (o < lanes_per_head) D += __shfl_xor(D, o);
         // this lane's share of <q_i, w_e> and <g_i, w_e> (dedge_w)
         float pq = 0.0f, pg = 0.0f;
 #pragma unroll
@@ -289,21 +292,21 @@ __global__ __launch_bounds__(256) void gsm_attn_bwd_target_kernel(
                 kj = *(const T *)(k + j * HC + ch);
                 vj = *(const T *)(v + j * HC + ch);
             }
-            float sc = 0.0f, gm = 0.0f;
+            float sc = 0.0f, gd = 0.0f;                      // gd = gm_ij - D_i
 #pragma unroll
             for (int i = 0; i < kVec; ++i) {
                 sc += V::get(qi, i) * (V::get(kj, i) + w * V::get(we, i));
-                gm += V::get(gi, i) * (V::get(vj, i) + w * V::get(we, i));
+                gd += V::get(gi, i) * ((V::get(vj, i) + w * V::get(we, i)) - V::get(om, i));
             }
 #pragma unroll
             for (int o = 1; o < kLP; o <<= 1)
                 if (o < lanes_per_head) {
                     sc += __shfl_xor(sc, o);
-                    gm += __shfl_xor(gm, o);
+                    gd += __shfl_xor(gd, o);
                 }
             sc *= scale;
             const float a = on ? __expf(sc - ls) : 0.0f;
-            const float ds = a * (gm - D);
+            const float ds = a * gd;
 #pragma unroll
             for (int i = 0; i < kVec; ++i)
                 V::set(acc, i, V::get(acc, i) + ds * (V::get(kj, i) + w * V::get(we, i)));

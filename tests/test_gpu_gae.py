@@ -25,7 +25,9 @@ def _loop(r, values, done, gamma, lam):
     return ret
 
 
-@pytest.mark.parametrize("N,B,T,ep", [(3, 7, 1, 100), (6, 20, 5, 2), (3, 101, 4, 2)])
+# the slot loop is unrolled by four: T = 2, 3, 7, 11 leave remainders 2 and 3, with and without a full trip
+@pytest.mark.parametrize("N,B,T,ep", [(3, 7, 1, 100), (6, 20, 5, 2), (3, 101, 4, 2),
+                                      (3, 7, 2, 100), (6, 20, 3, 2), (3, 101, 7, 3), (3, 9, 11, 4)])
 def test_kernel_returns_are_the_loop_bit_for_bit(N, B, T, ep):
     from gsmarl_amd import EnvConfig, GpuBatchEnv, GraphRolloutBuffer
     env = GpuBatchEnv(EnvConfig(n_agents=N, n_envs=B, seed=8, episode_length=ep), DEV)

@@ -46,6 +46,82 @@ def test_kernel_matches_reference(heads, C, edge, skip):
     assert torch.equal(out[empty], base[empty])          # no neighbours -> 0 (+ skip)
 
 
+# Scores that are exact in fp32 and far apart, so that the online softmax's
+# rescale from mx = -inf and across large jumps is what decides the result:
+# scale = 1, no edge term, q_i[h] = (8, 0, ..), k_j[h][0] an integer in
+# [-16, 16] (the head's other channels random: they meet q's zeros), so a score
+# is 8 * k_j[h][0], an integer in [-128, 128]; v random. A row has its own
+# sources, listed in the order of the pattern.
+ORDERED_SHAPES = [(1, 1), (2, 4), (3, 16)]
+PATTERNS = ("ascending", "descending", "middle", "equal", "tied")
+ORDERED_DEGS = (33,) * 10 + (300,) * 5                     # row r, head h: PATTERNS[(r + h) % 5]
+_ORDERED = {}
+
+
+def _pattern(name, d):
+    """k_j[h][0] along a row of d entries."""
+    t = np.arange(d)
+    if name == "ascending":                                 # every step raises the maximum (d = 33: by 8)
+        return np.round(np.linspace(-16, 16, d))
+    if name == "descending":
+        return np.round(np.linspace(16, -16, d))
+    if name == "middle":                                    # the maximum in the middle
+        return np.round(16 - 32 * np.abs(t - d // 2) / (d // 2))
+    if name == "equal":                                     # the output is the plain mean
+        return np.full(d, 3.0)
+    x = np.full(d, -4.0)                                    # two tied maxima 13 steps = 104 above the rest (the
+    x[[d // 6, (2 * d) // 3]] = 9.0                         # multiple of 8 next to 100): the rest weigh exp(-104)
+    return x
+
+
+def ordered_case(heads, C):
+    """The graph and inputs above; built once per shape and left unchanged."""
+    if (heads, C) in _ORDERED:
+        return _ORDERED[(heads, C)]
+    R, HC = len(ORDERED_DEGS), heads * C
+    n = R + sum(ORDERED_DEGS)
+    deg = np.zeros(n, np.int64)
+    deg[:R] = ORDERED_DEGS
+    ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(deg, out=ptr[1:])
+    col = np.arange(R, n, dtype=np.int32)                   # row r's sources: its own run of nodes
+    g = torch.Generator(device=DEV).manual_seed(11)
+    k, v, grad = (torch.randn(n, HC, device=DEV, generator=g) for _ in range(3))
+    q = torch.zeros(n, HC, device=DEV)
+    q[:, ::C] = 8.0
+    k0 = np.zeros((n - R, heads), np.float32)
+    equal = np.zeros((R, heads), bool)
+    for r, d in enumerate(ORDERED_DEGS):
+        for h in range(heads):
+            name = PATTERNS[(r + h) % 5]
+            k0[ptr[r]:ptr[r + 1], h] = _pattern(name, d)
+            equal[r, h] = name == "equal"
+    assert np.abs(k0).max() == 16 and np.array_equal(k0, np.round(k0))
+    k[R:, ::C] = torch.from_numpy(k0).to(DEV)
+    c = dict(heads=heads, C=C, R=R, q=q, k=k, v=v, g=grad, ptr=torch.from_numpy(ptr).to(DEV),
+             col=torch.from_numpy(col).to(DEV), equal=torch.from_numpy(equal).to(DEV))
+    c["ref"] = gnn.attn_aggregate_ref(q.double(), k.double(), v.double(), c["ptr"], c["col"], heads=heads, scale=1.0)
+    _ORDERED[(heads, C)] = c
+    return c
+
+
+@pytest.mark.parametrize("heads,C", ORDERED_SHAPES)
+def test_extreme_and_ordered_scores(heads, C):
+    c = ordered_case(heads, C)
+    R, ptr, ref = c["R"], c["ptr"], c["ref"]
+    out = gnn.attn_aggregate(c["q"], c["k"], c["v"], ptr, c["col"], heads=heads, scale=1.0)
+    err = (out.double() - ref).abs()
+    print(f"H{heads} C{C} ordered scores: worst normalised error {float((err / (1 + ref.abs())).max()):.3e}")
+    assert torch.all(err <= 2e-5 * (1 + ref.abs())), float(err.max())
+    assert torch.count_nonzero(out[R:]) == 0                # the sources' own rows are empty
+    # equal scores: the plain mean of the row's v
+    means = torch.stack([c["v"][int(ptr[r]) + R:int(ptr[r + 1]) + R].double().mean(0) for r in range(R)])
+    eq = c["equal"][:, :, None].expand(R, heads, C).reshape(R, heads * C)
+    assert int(c["equal"].sum()) >= 3 * heads
+    assert float((ref[:R] - means).abs()[eq].max()) <= 1e-12
+    assert torch.all(((out[:R].double() - means).abs() <= 2e-5 * (1 + means.abs()))[eq])
+
+
 def test_env_graph_headline_size():
     """Message passing over the env's own COO output (symmetric, row-major =
     CSR over targets) at 24 agents x 8192 envs."""

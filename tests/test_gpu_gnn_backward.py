@@ -8,7 +8,12 @@ Tolerance: the forward's criterion, err <= 2e-5 * (1 + |ref|) against fp64,
 for dq, dk, dv and dedge_w. dw_e sums one term per edge and channel, so its
 bound scales with the sum of the terms' magnitudes: err <= 2e-5 * (1 +
 sum_ij |edge_w_ij de_ij[c]|). The fp32 torch formulation's autograd error
-against the same fp64 reference is measured alongside and printed."""
+against the same fp64 reference is measured alongside and printed.
+
+The same recipe and bounds at sizes past the target kernel's grid cap (CAPPED:
+a workgroup walks several node groups, the dw_e sum takes several rounds), with
+the edge projection frozen (no dw_e partials at all), and on rows of exact,
+ordered, far-apart scores (test_gpu_gnn.ordered_case)."""
 import functools
 import math
 
@@ -17,6 +22,8 @@ import pytest
 import torch
 
 from gsmarl_amd import gnn
+from test_gnn_dispatch_ref import select
+from test_gpu_gnn import ORDERED_SHAPES, ordered_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -26,6 +33,13 @@ HUB, LONG, LOOP, DUP, NEVER = 5, 17, 20, 30, 77
 SHAPES = [(1, 1), (3, 2), (1, 4), (2, 8), (3, 16), (4, 16), (1, 64)]
 OPTS = [(True, True), (False, False)]
 NAMES = ("dq", "dk", "dv", "dedge_w", "dw_e", "dskip")
+BWD_MAX_BLOCKS = 1280                                         # kBwdMaxBlocks: the target kernel's grid cap
+BWD_SUM_ROUND = 128                                           # 8 * kBwdSumRows: partials per round of the dw_e sum
+# (heads, C, n): n = nodes per group * full groups + a remainder (a ragged last wave)
+CAPPED = [(4, 16, 16 * 301 + 3),       # 302 partials, no stride: three sum rounds, the last one partial
+          (4, 16, 16 * 2860 + 5),      # 2861 groups: workgroups 0..300 walk three, the others two; ten full rounds
+          (3, 2, 32 * 1357 + 9),       # (8, 1) with dead lanes, capped
+          (1, 1, 256 * 1290 + 17)]     # (1, 1), capped
 
 
 def _graph(n, rng, max_deg=6, empty=0.2):
@@ -67,11 +81,19 @@ def _edge_term_sums(g, q, k, v, ptr, col, ew, we, heads):
     return (ew[:, None] * de).abs().sum(0)
 
 
-def _run_kernel(c, transpose, edge_grad=True):
+def _groups(heads, C, n):
+    """Node groups of the target kernel: four waves of 64 / LP nodes each."""
+    per_group = 4 * (64 // select(heads, C)[0])
+    return -(-n // per_group), per_group
+
+
+def _run_kernel(c, transpose, edge_grad=True, frozen=()):
     ins = {n_: (c[n_].clone().requires_grad_(True) if c[n_] is not None else None)
            for n_ in ("q", "k", "v", "ew", "we", "sk")}
     if not edge_grad and ins["ew"] is not None:
         ins["ew"].requires_grad_(False)
+    for n_ in frozen:
+        ins[n_].requires_grad_(False)
     out = gnn.attn_aggregate_autograd(ins["q"], ins["k"], ins["v"], c["ptr"], c["col"], ins["ew"], ins["we"],
                                       ins["sk"], c["heads"], transpose=transpose)
     out.backward(c["g"])
@@ -80,12 +102,12 @@ def _run_kernel(c, transpose, edge_grad=True):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(heads, C, edge, skip):
+def _case(heads, C, edge, skip, n=N):
     rng = np.random.default_rng(heads * 100 + C)
-    ptr, col = _graph(N, rng)
+    ptr, col = _graph(n, rng)
     HC = heads * C
     gen = torch.Generator(device=DEV).manual_seed(3)
-    q, k, v, sk, g = (torch.randn(N, HC, device=DEV, generator=gen) for _ in range(5))
+    q, k, v, sk, g = (torch.randn(n, HC, device=DEV, generator=gen) for _ in range(5))
     c = dict(heads=heads, ptr=ptr, col=col, q=q, k=k, v=v, g=g,
              ew=torch.rand(col.numel(), device=DEV, generator=gen) if edge else None,
              we=torch.randn(HC, device=DEV, generator=gen) if edge else None, sk=sk if skip else None)
@@ -120,17 +142,25 @@ def _norm_err(c, grads):
 @pytest.mark.parametrize("heads,C", SHAPES)
 @pytest.mark.parametrize("edge,skip", OPTS)
 def test_backward_matches_reference(heads, C, edge, skip):
-    c = _case(heads, C, edge, skip)
+    _matches_reference(_case(heads, C, edge, skip), heads, C, edge, skip)
+
+
+def _matches_reference(c, heads, C, edge, skip):
     kern, torch32 = _norm_err(c, c["grads"]), _norm_err(c, c["torch32"])
-    print(f"H{heads} C{C} edge={edge} skip={skip} normalised max error vs fp64: kernel {kern} | torch fp32 {torch32}")
+    print(f"H{heads} C{C} n={c['q'].shape[0]} edge={edge} skip={skip} normalised max error vs fp64: "
+          f"kernel {kern} | torch fp32 {torch32}")
     for name, e in kern.items():
         assert e <= BOUND, (name, e, torch32[name])
+    return kern
 
 
 @pytest.mark.parametrize("heads,C", SHAPES)
 @pytest.mark.parametrize("edge,skip", OPTS)
 def test_exact_rows_and_forward(heads, C, edge, skip):
-    c = _case(heads, C, edge, skip)
+    _exact_rows_and_forward(_case(heads, C, edge, skip), heads, skip)
+
+
+def _exact_rows_and_forward(c, heads, skip):
     dq, dk, dv, _, _, dsk = c["grads"]
     if skip:
         assert torch.equal(dsk, c["g"])                             # dskip is grad_out, bitwise
@@ -147,7 +177,10 @@ def test_exact_rows_and_forward(heads, C, edge, skip):
 @pytest.mark.parametrize("heads,C", SHAPES)
 @pytest.mark.parametrize("edge,skip", OPTS)
 def test_backward_is_reproducible(heads, C, edge, skip):
-    c = _case(heads, C, edge, skip)
+    _is_reproducible(_case(heads, C, edge, skip))
+
+
+def _is_reproducible(c):
     out, again = _run_kernel(c, None)                               # the transpose built inside this time
     assert torch.equal(out, c["out"])
     for name, a, b in zip(NAMES, again, c["grads"]):
@@ -161,6 +194,86 @@ def test_edge_weight_without_grad():
     for a, b in zip((dq, dk, dv, dwe, dsk), [c["grads"][i] for i in (0, 1, 2, 4, 5)]):
         assert torch.equal(a, b)
     assert _norm_err(c, (dq, dk, dv, c["grads"][3], dwe, dsk))["dw_e"] <= BOUND
+
+
+@pytest.mark.parametrize("heads,C", [(3, 16), (3, 2)])
+def test_edge_projection_without_grad(heads, C):
+    """w_e frozen, everything else live: the kernel gets no dw_e, so no partial
+    rows and no LDS reduction; every other gradient is the all-live run's."""
+    c = _case(heads, C, True, True)
+    out, (dq, dk, dv, dew, dwe, dsk) = _run_kernel(c, c["transpose"], frozen=("we",))
+    assert dwe is None
+    assert torch.equal(out, c["out"])
+    for name, a, b in zip(("dq", "dk", "dv", "dedge_w", "dskip"), (dq, dk, dv, dew, dsk),
+                          [c["grads"][i] for i in (0, 1, 2, 3, 5)]):
+        assert a is not None and torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("heads,C,n", CAPPED)
+@pytest.mark.parametrize("edge,skip", OPTS)
+def test_backward_beyond_the_grid_cap(heads, C, n, edge, skip):
+    """The whole criterion set of the n = 1003 tests where the target kernel's
+    grid-stride loop takes further trips and the dw_e sum further rounds."""
+    groups, per_group = _groups(heads, C, n)
+    assert n % per_group and (n % per_group) % (per_group // 4)  # a partial last group with a ragged last wave
+    if n == CAPPED[0][2]:
+        # every group has its own workgroup; the partials take three rounds, the last one partial
+        assert BWD_SUM_ROUND < groups == 302 <= BWD_MAX_BLOCKS
+        assert -(-groups // BWD_SUM_ROUND) == 3 and groups % BWD_SUM_ROUND
+    else:
+        assert groups > BWD_MAX_BLOCKS                      # the stride loop takes a second trip
+        assert BWD_MAX_BLOCKS % BWD_SUM_ROUND == 0 and BWD_MAX_BLOCKS // BWD_SUM_ROUND == 10
+        assert groups % BWD_MAX_BLOCKS                      # and the workgroups walk unequal numbers of groups
+    if (heads, C, n) == CAPPED[1]:
+        assert groups == 2861 and groups - 2 * BWD_MAX_BLOCKS == 301
+    assert _groups(heads, C, N)[0] <= BWD_SUM_ROUND         # what the n = 1003 tests reach: one trip, one round
+    c = _case(heads, C, edge, skip, n)
+    _matches_reference(c, heads, C, edge, skip)
+    _exact_rows_and_forward(c, heads, skip)
+    _is_reproducible(c)                                     # bitwise, dw_e included
+
+
+@pytest.mark.parametrize("heads,C", ORDERED_SHAPES)
+def test_extreme_and_ordered_scores(heads, C):
+    """test_gpu_gnn.ordered_case: exact integer scores in [-128, 128] in rows of
+    33 and 300 entries (ascending, descending, maximum in the middle, all
+    equal, two tied maxima 104 above the rest). D_i is formed from the rounded
+    output, so the criterion is test_gpu_env_conv's for its spread layout:
+    E_kernel <= max(2e-5, 4 * E_torch32), both normalised errors against fp64.
+
+    This is the regression test of the form the target kernel evaluates ds_ij
+    in: a_ij * <g_i, m_ij - (out_i - skip_i)>, the difference taken per channel
+    before the dot product. With a_ij * (<g_i, m_ij> - D_i), D_i a dot product
+    of its own, dq at 3 x 16 measured 2.27e-5 (torch fp32 2.08e-6) and missed
+    the criterion: on a row that one entry dominates, the rounding of two
+    16-term dot products of magnitude ~4 stayed in their difference, and
+    dq_i[c] = sum_j ds_ij k_j[c] multiplied it by |k_j| = 16 in each head's
+    channel 0 (the other channels stayed below 1.6e-6).
+
+    Measured on an MI355X (kernel | torch fp32): 1x1 dq 1.05e-6 | 2.9e-7, dk
+    9.6e-7 | 1.1e-7, dv 3.9e-7 | 1.3e-8; 2x4 dq 9.41e-6 | 1.79e-6, dk 2.60e-6 |
+    2.2e-7, dv 6.6e-7 | 4.8e-8; 3x16 dq 7.77e-6 | 2.08e-6, dk 2.92e-6 | 4.3e-7,
+    dv 8.9e-7 | 4.3e-8. What is left is the rounding of the forward's fp32
+    out_i (half an ulp a channel) times |k_j|."""
+    c = ordered_case(heads, C)
+    q, k, v, g, ptr, col = (c[n_] for n_ in ("q", "k", "v", "g", "ptr", "col"))
+    ins = [t.clone().requires_grad_(True) for t in (q, k, v)]
+    out = gnn.attn_aggregate_autograd(*ins, ptr, col, heads=heads, scale=1.0)
+    out.backward(g)
+    assert torch.equal(out.detach(), gnn.attn_aggregate(q, k, v, ptr, col, heads=heads, scale=1.0))
+    ref = gnn.attn_aggregate_bwd_ref(g.double(), q.double(), k.double(), v.double(), ptr, col, heads=heads, scale=1.0)
+    t32 = [t.clone().requires_grad_(True) for t in (q, k, v)]
+    gnn.attn_aggregate_ref(*t32, ptr, col, heads=heads, scale=1.0).backward(g)
+    errs = []
+    for name, a, b, r in zip(NAMES, ins, t32, ref):
+        e_k = float(((a.grad.double() - r).abs() / (1 + r.abs())).max())
+        e_t = float(((b.grad.double() - r).abs() / (1 + r.abs())).max())
+        print(f"H{heads} C{C} ordered scores {name}: kernel {e_k:.3e} torch fp32 {e_t:.3e}")
+        errs.append((name, e_k, e_t))
+    for name, e_k, e_t in errs:
+        assert e_k <= max(BOUND, 4 * e_t), (name, e_k, e_t)
+    assert torch.count_nonzero(ins[0].grad[c["R"]:]) == 0   # the sources' own rows are empty
+    assert torch.count_nonzero(ins[1].grad[:c["R"]]) == 0   # the targets are nobody's source
 
 
 def test_output_has_grad_fn_and_no_double_backward():

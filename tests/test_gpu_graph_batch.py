@@ -134,6 +134,79 @@ def test_sample_without_entries(small):
         small.edge_ptr[2].copy_(keep)
 
 
+# gsm_graph_batch_ptr's scan: 8 samples a thread, 512 a wave, 8192 a chunk (one
+# workgroup of 1024 threads), a cross-wave sum in LDS and a carry between chunks
+SCAN_WAVE, SCAN_CHUNK = 512, 8192
+
+
+def _many(buf, K, seed=0):
+    """K random samples of `buf`, with (0, 0) and (T, B-1) alternating at the
+    first and last sample and on both sides of the first wave and chunk
+    boundaries."""
+    gen = torch.Generator().manual_seed(1000 + K + seed)
+    t = torch.randint(0, buf.T + 1, (K,), generator=gen)
+    b = torch.randint(0, buf.B, (K,), generator=gen)
+    spots = [p for p in (0, SCAN_WAVE - 1, SCAN_WAVE, SCAN_CHUNK - 1, SCAN_CHUNK, K - 1) if p < K]
+    for i, p in enumerate(spots):
+        t[p], b[p] = (0, 0) if i % 2 == 0 else (buf.T, buf.B - 1)
+    return t, b
+
+
+@pytest.mark.parametrize("K", [513, 8192, 8193, 8709, 16387])
+def test_scan_across_waves_and_chunks(small, K):
+    """More samples than two threads hold: the wave scan beyond lane 1, the
+    cross-wave sum (K > 512) and the carry into a second and a third chunk
+    (K > 8192, K > 16384), each with a ragged end."""
+    assert small.E == 9 and (small.T, small.B) == (3, 50)
+    c = _check(small, *_many(small, K))
+    assert c["ptr"].numel() == K + 1 and c["node_feat"].shape[0] == K * 9
+
+
+def test_scan_with_empty_samples_at_the_boundaries(small):
+    """Slot 2 without entries: about a quarter of the samples count zero, on
+    both sides of the wave and chunk boundaries."""
+    K = 8709
+    t, b = _many(small, K, seed=1)
+    for p in (SCAN_WAVE - 2, SCAN_WAVE + 1, SCAN_CHUNK - 2, SCAN_CHUNK + 1, K - 2):
+        t[p] = 2
+    assert int((t == 2).sum()) > K // 8
+    keep = small.edge_ptr[2].clone()
+    try:
+        small.edge_ptr[2].zero_()
+        c = _check(small, t, b)
+        cnt = c["ptr"][1:] - c["ptr"][:-1]
+        assert bool((cnt[(t == 2).to(cnt.device)] == 0).all()) and bool((cnt[(t != 2).to(cnt.device)] > 0).any())
+    finally:
+        small.edge_ptr[2].copy_(keep)
+
+
+def test_bad_sample_in_the_second_chunk(small):
+    """One bad index, and one truncated sample, at k = 8200 among valid ones:
+    the status bits of a thread far from the first reach the host."""
+    K, k_bad = 8709, 8200
+    t, b = _many(small, K, seed=2)
+    for tb, bb in ((4, 0), (0, 50), (-1, 3)):
+        t2, b2 = t.clone(), b.clone()
+        t2[k_bad], b2[k_bad] = tb, bb
+        with pytest.raises(IndexError):
+            small.graph_batch_csr(t2, b2)
+    _check(small, t[k_bad - 3:k_bad + 3], b[k_bad - 3:k_bad + 3])   # the samples around it are valid
+    env, buf = _filled(1, n_agents=24, n_envs=32, seed=5, edges_per_env=8)
+    try:
+        assert bool(buf.overflowed())
+        whole = (buf.edge_ptr[:, 1:] <= buf.cap).nonzero()       # (t, b) of the samples inside the capacity
+        cut = (buf.edge_ptr[:, 1:] > buf.cap).nonzero()
+        assert whole.shape[0] >= 2 and cut.shape[0] >= 1
+        pick = torch.randint(0, whole.shape[0], (K,), generator=torch.Generator().manual_seed(3))
+        t, b = whole[:, 0].cpu()[pick], whole[:, 1].cpu()[pick]
+        assert int(buf.graph_batch_csr(t, b)["status"].item()) == 0
+        t[k_bad], b[k_bad] = int(cut[-1, 0]), int(cut[-1, 1])
+        with pytest.raises(ValueError, match="capacity"):
+            buf.graph_batch_csr(t, b)
+    finally:
+        env.close()
+
+
 def test_no_samples(small):
     e = torch.zeros(0, dtype=torch.int64)
     c = small.graph_batch_csr(e, e)
