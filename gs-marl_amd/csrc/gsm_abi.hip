@@ -1642,6 +1642,116 @@ int gsm_env_conv_bwd(const float *grad_out, const float *node_feat, const int64_
     return GSM_OK;
 }
 
+// the shape limits of the actor head, before anything else is looked at
+static int actor_shape(int64_t x_row_stride, int64_t n_envs, int32_t n_agents, int32_t in_features, int32_t hidden,
+                       int32_t n_actions) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (in_features < 4 || in_features > 128 || in_features % 4)
+        return fail(nullptr, GSM_EINVAL, "in_features must be a multiple of 4 in [4, 128]");
+    if (hidden != 0 && hidden != 16 && hidden != 32 && hidden != 64)
+        return fail(nullptr, GSM_EINVAL, "hidden must be 0, 16, 32 or 64");
+    if (n_actions < 2 || n_actions > 8) return fail(nullptr, GSM_EINVAL, "n_actions must be in [2, 8]");
+    if (n_agents < 1 || n_envs < 0 || n_envs >= lim || n_envs * n_agents >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_agents >= 1, n_envs >= 0 and n_envs*n_agents < 2^31");
+    if (x_row_stride < in_features || x_row_stride % 4)
+        return fail(nullptr, GSM_EINVAL, "x_row_stride must be a multiple of 4 and >= in_features");
+    return GSM_OK;
+}
+
+static int actor_pointers(const float *x, const float *w1, const float *b1, const float *w2, const float *b2,
+                          int32_t hidden) {
+    if (!x || !w2 || !b2 || (hidden && (!w1 || !b1))) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    if ((uintptr_t)x % 16) return fail(nullptr, GSM_EINVAL, "x must be 16-byte aligned");
+    return GSM_OK;
+}
+
+static gsm::ActorParams actor_params(const float *x, int64_t x_row_stride, const float *w1, const float *b1,
+                                     const float *w2, const float *b2, int64_t n_envs, int32_t n_agents,
+                                     int32_t in_features, int32_t n_actions, int32_t *status) {
+    gsm::ActorParams p = {};
+    p.x = x;
+    p.x_stride = x_row_stride;
+    p.w1 = w1, p.b1 = b1, p.w2 = w2, p.b2 = b2;
+    p.R = (int)(n_envs * n_agents);
+    p.n_agents = n_agents;
+    p.in = in_features;
+    p.nA = n_actions;
+    p.status = status;
+    return p;
+}
+
+int gsm_actor_sample(const float *x, int64_t x_row_stride, const float *w1, const float *b1, const float *w2,
+                     const float *b2, int64_t n_envs, int32_t n_agents, int32_t in_features, int32_t hidden,
+                     int32_t n_actions, uint64_t seed, int64_t env_base, int64_t draw_host, const int64_t *draw_dev,
+                     int32_t flags, int32_t *actions, float *logp, float *entropy, float *logits_out,
+                     int32_t *status, void *stream) {
+    if (const int rc = actor_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_actions)) return rc;
+    if (flags & ~GSM_ACTOR_DETERMINISTIC) return fail(nullptr, GSM_EINVAL, "unknown flags");
+    if (n_envs == 0) return GSM_OK;
+    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (!actions || !logp) return fail(nullptr, GSM_EINVAL, "actions or logp is NULL");
+    gsm::ActorParams p = actor_params(x, x_row_stride, w1, b1, w2, b2, n_envs, n_agents, in_features, n_actions,
+                                      status);
+    p.k0 = (uint32_t)seed, p.k1 = (uint32_t)(seed >> 32);
+    p.env_base = env_base, p.draw_host = draw_host, p.draw_dev = draw_dev;
+    p.deterministic = (flags & GSM_ACTOR_DETERMINISTIC) != 0;
+    p.actions_out = actions, p.logp = logp, p.entropy = entropy, p.logits_out = logits_out;
+    const hipError_t e = gsm::launch_actor_forward(p, hidden, false, as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_sample launch");
+    return GSM_OK;
+}
+
+int gsm_actor_eval(const float *x, int64_t x_row_stride, const float *w1, const float *b1, const float *w2,
+                   const float *b2, int64_t n_envs, int32_t n_agents, int32_t in_features, int32_t hidden,
+                   int32_t n_actions, const int32_t *actions, float *logp, float *entropy, int32_t *status,
+                   void *stream) {
+    if (const int rc = actor_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_actions)) return rc;
+    if (n_envs == 0) return GSM_OK;
+    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (!actions || !logp) return fail(nullptr, GSM_EINVAL, "actions or logp is NULL");
+    gsm::ActorParams p = actor_params(x, x_row_stride, w1, b1, w2, b2, n_envs, n_agents, in_features, n_actions,
+                                      status);
+    p.actions_in = actions, p.logp = logp, p.entropy = entropy;
+    const hipError_t e = gsm::launch_actor_forward(p, hidden, true, as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_eval launch");
+    return GSM_OK;
+}
+
+int gsm_actor_backward_work_floats(int32_t in_features, int32_t hidden, int32_t n_actions, int64_t *n_floats) {
+    if (const int rc = actor_shape(in_features, 0, 1, in_features, hidden, n_actions)) return rc;
+    if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
+    *n_floats = gsm::actor_backward_work_floats(in_features, hidden, n_actions);
+    return GSM_OK;
+}
+
+int gsm_actor_eval_bwd(const float *g_logp, const float *g_ent, const float *x, int64_t x_row_stride,
+                       const float *w1, const float *b1, const float *w2, const float *b2, int64_t n_envs,
+                       int32_t n_agents, int32_t in_features, int32_t hidden, int32_t n_actions,
+                       const int32_t *actions, float *work, float *dw1, float *db1, float *dw2, float *db2,
+                       float *dx, int32_t *status, void *stream) {
+    if (const int rc = actor_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_actions)) return rc;
+    if (!dw2 || !db2 || (hidden && (!dw1 || !db1))) return fail(nullptr, GSM_EINVAL, "a gradient pointer is NULL");
+    hipStream_t s = as_stream(stream);
+    if (n_envs == 0) {
+        const size_t f = sizeof(float);
+        hipError_t e = hipMemsetAsync(dw2, 0, f * n_actions * (hidden ? hidden : in_features), s);
+        if (e == hipSuccess) e = hipMemsetAsync(db2, 0, f * n_actions, s);
+        if (hidden && e == hipSuccess) e = hipMemsetAsync(dw1, 0, f * hidden * in_features, s);
+        if (hidden && e == hipSuccess) e = hipMemsetAsync(db1, 0, f * hidden, s);
+        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_eval_bwd memset");
+        return GSM_OK;
+    }
+    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (!g_logp || !actions || !work) return fail(nullptr, GSM_EINVAL, "g_logp, actions or work is NULL");
+    if ((uintptr_t)dx % 16) return fail(nullptr, GSM_EINVAL, "dx must be 16-byte aligned");
+    gsm::ActorParams p = actor_params(x, x_row_stride, w1, b1, w2, b2, n_envs, n_agents, in_features, n_actions,
+                                      status);
+    p.actions_in = actions, p.g_logp = g_logp, p.g_ent = g_ent, p.dx = dx, p.part = work;
+    const hipError_t e = gsm::launch_actor_backward(p, hidden, dw1, db1, dw2, db2, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_eval_bwd launch");
+    return GSM_OK;
+}
+
 int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
             int32_t n_agents, float gamma, float gamma_lambda, float *ret, void *stream) {
     const int64_t lim = (int64_t)1 << 31;

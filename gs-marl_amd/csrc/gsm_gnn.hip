@@ -1577,3 +1577,6 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
 }
 
 }  // namespace gsm
+
+// the actor head: gsm_actor_sample / gsm_actor_eval / gsm_actor_eval_bwd
+#include "gsm_actor.h"

@@ -305,6 +305,31 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
                                     const float *lse, int64_t B, int E, int HC, int C, float scale, bool skip,
                                     int n_rows_out, float *work, float *dw, float *dw_e, int32_t *status,
                                     hipStream_t s);
+// the actor head (gsm_actor.h): what its three launchers take. R = n_envs *
+// n_agents rows; k0, k1 the seed's halves; the forward reads actions_in (eval)
+// or writes actions_out (sample); part: the backward's partials in `work`
+struct ActorParams {
+    const float *x;
+    int64_t x_stride;
+    const float *w1, *b1, *w2, *b2;
+    int R, n_agents, in, nA;
+    uint32_t k0, k1;
+    int64_t env_base, draw_host;
+    const int64_t *draw_dev;
+    int deterministic;
+    const int32_t *actions_in;
+    int32_t *actions_out;
+    float *logp, *entropy, *logits_out;
+    int32_t *status;
+    const float *g_logp, *g_ent;
+    float *dx, *part;
+};
+hipError_t launch_actor_forward(const ActorParams &p, int hidden, bool eval, hipStream_t s);
+// floats of workspace launch_actor_backward needs: one partial (dw1, db1, dw2,
+// db2) per workgroup of its capped grid
+int64_t actor_backward_work_floats(int in, int hidden, int nA);
+hipError_t launch_actor_backward(const ActorParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
+                                 hipStream_t s);
 hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
                       float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,

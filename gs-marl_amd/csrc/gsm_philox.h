@@ -14,7 +14,9 @@
 
 namespace gsm {
 
-enum : uint32_t { kTagLayout = 0u, kTagActions = 1u, kTagShape = 2u };
+// kTagPolicy: the actor head's action draw, counter = (agent, draw, global env
+// id, TAG) (gsm_actor_sample in include/gsm.h)
+enum : uint32_t { kTagLayout = 0u, kTagActions = 1u, kTagShape = 2u, kTagPolicy = 3u };
 
 struct Philox4 { uint32_t x0, x1, x2, x3; };
 

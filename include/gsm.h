@@ -534,6 +534,82 @@ int gsm_env_conv_bwd(const float *grad_out, const float *node_feat, const int64_
                      int32_t n_entities, int32_t heads, int32_t channels, float scale, int32_t flags,
                      int32_t n_rows_out, float *work, float *dw, float *dw_e, int32_t *status, void *stream);
 
+/* The actor head: policy features -> MLP -> categorical distribution -> the
+ * sampled action and its log-probability (the rollout) or log-probability and
+ * entropy of stored actions with their gradients (the PPO / Lagrangian
+ * update), one launch each. Rows r = b*n_agents + i, R = n_envs*n_agents.
+ * x f32, row r at x + r*x_row_stride (floats; x_row_stride >= in_features and
+ * a multiple of 4, the base 16-byte aligned: a view of gsm_env_conv's out
+ * works). w1 f32 [hidden][in_features], b1 [hidden], w2 [n_actions][hidden],
+ * b2 [n_actions] (the torch.nn.Linear layout):
+ *   h = relu(W1 x + b1);  logits l = W2 h + b2
+ * hidden == 0 is a linear head: w2 [n_actions][in_features], w1 = b1 = NULL.
+ * Every dot product is one accumulation chain of explicit fmaf (one rounding
+ * a step; the library is built with -ffp-contract=off, nothing else fuses)
+ * that starts from the bias and takes the inputs in ascending index; relu(v)
+ * = v < 0 ? 0 : v. The same chain in all three entry points.
+ * The distribution, one correctly ordered fp32 operation a line:
+ *   m = max_a l_a;  e_a = expf(l_a - m);  s = e_0 + e_1 + .. (ascending)
+ *   logp_a = (l_a - m) - logf(s)
+ *   entropy = logf(s) - (sum_a e_a * (l_a - m)) / s   (the sum ascending)
+ * The draw: one Philox4x32-10 call per row, counter = (i, (uint32)draw,
+ * (uint32)(env_base + b), kTagPolicy = 3), key = (seed lo32, seed hi32), u =
+ * (x0 >> 8) * 2^-24; draw = draw_host + (draw_dev ? *draw_dev : 0), draw_dev a
+ * device int64 [1] the kernel only reads (a counter a captured graph advances
+ * on the device). A shard with env_base = b0 draws what rows b0.. of the full
+ * batch draw. The sample: t = u * s; c = 0; for a ascending c = c + e_a; the
+ * action is the first a with t < c, n_actions - 1 if none (u * s can round up
+ * to s). With GSM_ACTOR_DETERMINISTIC the action is the lowest index that
+ * attains m and nothing is drawn.
+ * A row with a non-finite logit gets action 0, logp = entropy = NaN and ORs
+ * GSM_ACTOR_NONFINITE into status (device int32 [1], zeroed by the caller;
+ * NULL: not wanted); the other rows are not affected.
+ *
+ * gsm_actor_sample: actions int32 [R] (what gsm_step takes with
+ * GSM_ACT_INDEX), logp f32 [R] of the chosen action, entropy f32 [R] or NULL,
+ * logits_out f32 [R][n_actions] or NULL.
+ * gsm_actor_eval: the same head on stored actions int32 [R]: logp f32 [R],
+ * entropy f32 [R] or NULL. An action outside [0, n_actions) sets
+ * GSM_ACTOR_BAD_ACTION and gets logp = NaN. For the same inputs the logp of
+ * the actions gsm_actor_sample chose is bit-identical to the logp it returned
+ * (either mode): the PPO ratio is exactly 1 before the first update.
+ * gsm_actor_eval_bwd: g_logp f32 [R], g_ent f32 [R] or NULL (zeros). h, the
+ * logits and p_a = e_a / s are recomputed on chip. With H the entropy:
+ *   dlogit_a = g_logp * (1[a = action] - p_a) - g_ent * p_a * (logp_a + H)
+ *   db2 = sum_r dlogit;  dW2 = sum_r dlogit (x) h
+ *   dh = W2^T dlogit where h > 0, else 0
+ *   db1 = sum_r dh;  dW1 = sum_r dh (x) x;  dx = W1^T dh
+ * (hidden == 0: dW2 = sum_r dlogit (x) x, dx = W2^T dlogit; dw1 = db1 = NULL).
+ * dw1, db1, dw2, db2 in the weights' layouts; dx f32 [R][in_features],
+ * 16-byte aligned, or NULL (not wanted). An action outside [0, n_actions)
+ * sets GSM_ACTOR_BAD_ACTION and has no indicator term; a non-finite row sets
+ * GSM_ACTOR_NONFINITE and its NaN reaches the gradients as autograd's would.
+ * work: device f32, gsm_actor_backward_work_floats of them (one partial per
+ * workgroup of a capped grid). No float atomics; the summation order depends
+ * on the shape alone, so the gradients are bitwise reproducible. With n_envs
+ * == 0 the weight gradients are zeros and nothing else is launched.
+ * Shape limits (GSM_EINVAL, checked first): in_features a multiple of 4 in
+ * [4, 128]; hidden 0, 16, 32 or 64; n_actions in [2, 8]; n_envs*n_agents <
+ * 2^31; x_row_stride as above. Stateless; asynchronous on `stream`. */
+#define GSM_ACTOR_DETERMINISTIC 1 /* flags: argmax, no draw                    */
+#define GSM_ACTOR_NONFINITE 1     /* status: a row had a non-finite logit      */
+#define GSM_ACTOR_BAD_ACTION 2    /* status: a stored action out of range      */
+int gsm_actor_sample(const float *x, int64_t x_row_stride, const float *w1, const float *b1, const float *w2,
+                     const float *b2, int64_t n_envs, int32_t n_agents, int32_t in_features, int32_t hidden,
+                     int32_t n_actions, uint64_t seed, int64_t env_base, int64_t draw_host, const int64_t *draw_dev,
+                     int32_t flags, int32_t *actions, float *logp, float *entropy, float *logits_out,
+                     int32_t *status, void *stream);
+int gsm_actor_eval(const float *x, int64_t x_row_stride, const float *w1, const float *b1, const float *w2,
+                   const float *b2, int64_t n_envs, int32_t n_agents, int32_t in_features, int32_t hidden,
+                   int32_t n_actions, const int32_t *actions, float *logp, float *entropy, int32_t *status,
+                   void *stream);
+int gsm_actor_backward_work_floats(int32_t in_features, int32_t hidden, int32_t n_actions, int64_t *n_floats);
+int gsm_actor_eval_bwd(const float *g_logp, const float *g_ent, const float *x, int64_t x_row_stride,
+                       const float *w1, const float *b1, const float *w2, const float *b2, int64_t n_envs,
+                       int32_t n_agents, int32_t in_features, int32_t hidden, int32_t n_actions,
+                       const int32_t *actions, float *work, float *dw1, float *db1, float *dw2, float *db2,
+                       float *dx, int32_t *status, void *stream);
+
 /* GAE returns of a stored episode of T = n_steps actions in one launch, with
  * BN = [n_envs][n_agents]: reward f32 [T]BN (entry t: the reward of action t),
  * value f32 [T+1]BN, done uint8 [T+1][n_envs] (slot t+1: action t ended the
