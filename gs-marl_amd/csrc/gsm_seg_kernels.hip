@@ -625,6 +625,44 @@ __device__ __forceinline__ void write_staged(const Lane &L, const float2 *s_pos,
     }
 }
 
+// Two envs per wave (gsm_roll_pair_kernel): both envs' staged rows as one
+// list. A word is (source | destination << 8 | skip << 16): entities of both
+// envs in one index space [0, 2E) (env B's are its own + E, positions and
+// global node ids alike: g0 is env A's first node), and `skip` the goal rows
+// that precede the edge in the output but are not staged, so edge e goes to
+// base + e + skip. The goal rows (goal -> own agent, one per agent lane) are
+// stored by their lanes directly: `goal` lanes write (g0 + gent, g0 + gent -
+// kN) at goal_at >= base, the distance from the same two positions in the same
+// operations as the pass.
+template <int kN>
+__device__ __forceinline__ void write_staged_pair(int lane, const float2 *s_pos, const uint32_t *s_scr, int total,
+                                                  int64_t base, int32_t g0, bool goal, int64_t goal_at,
+                                                  uint32_t gent, const EdgeSink &out) {
+    auto lists = [&](char *isrc, char *idst, char *attr, uint32_t wb) {
+        auto put = [&](uint32_t at, uint32_t a, uint32_t b) {
+            const float2 pa = s_pos[a], pb = s_pos[b];
+            const float dx = pa.x - pb.x, dy = pa.y - pb.y;
+            uint32_t byte = at << 2;
+            asm("" : "+v"(byte));   // keeps the stores in SGPR-base + 32-bit-offset form
+            *(int32_t *)(isrc + byte) = g0 + (int32_t)a;
+            *(int32_t *)(idst + byte) = g0 + (int32_t)b;
+            *(float *)(attr + byte) = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+        };
+        if (goal) put(wb + (uint32_t)(goal_at - base), gent, gent - (uint32_t)kN);
+        for (int e = lane; e < total; e += kWave) {
+            const uint32_t w = s_scr[e];
+            put(wb + (uint32_t)e + (w >> 16), w & 0xffu, (w >> 8) & 0xffu);
+        }
+    };
+    if (out.cap < ((int64_t)1 << 29)) {
+        // SGPR base (the sink's arrays) + 32-bit VGPR byte offset (the list's
+        // offset and the edge): 8 * cap < 2^32 bytes
+        lists((char *)out.index, (char *)(out.index + out.cap), (char *)out.attr, (uint32_t)base);
+        return;
+    }
+    lists((char *)(out.index + base), (char *)(out.index + out.cap + base), (char *)(out.attr + base), 0u);
+}
+
 // CSR offsets of a workgroup's envs: its edge counts (lane k < envs of the
 // block: env first+k) and the sum of the preceding workgroups' edge sums
 // (int4 loads spread over the workgroup's threads). Loads only; the sums are
@@ -1782,11 +1820,17 @@ __global__ __launch_bounds__(kBlock) GSM_ROLL_ATTR void gsm_roll_seg_kernel(DevP
 // outputs): every output is bit-identical to that kernel's.
 #define GSM_PAIR_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 constexpr int kPairHalf = 32, kPairEnvs = 2 * kWavesPerBlock;   // lanes per env, envs per workgroup
-// LDS per env: [positions E] x 3, [staging scratch 28 E] (roll_lds_*), [next
-// forces N], [obstacle column pairs No]; per wave: two of those, then the row
-// masks of step k - 2 (agent rows, obstacle rows) and their scan, per lane
-constexpr int pair_lds_env(int N, int No, int E) { return roll_lds_force(E) + 8 * N + 8 * No; }
-constexpr int pair_lds_wave(int N, int No, int E) { return 2 * pair_lds_env(N, No, E) + (8 + 8 + 4) * kWave; }
+// LDS per wave, each part env A's directly followed by env B's, so that the
+// emission addresses both envs in one index space (entity 0 .. 2E - 1, staged
+// word 0 .. both lists): [positions 2 E] x 3, [staging scratch 2 x 28 E],
+// [next forces 2 N], [obstacle column pairs 2 No]; then the row masks of step
+// k - 2 (agent rows, obstacle rows) and their scan, per lane
+constexpr int pair_lds_scr(int E) { return (3 * 2 * 8 * E + 15) & ~15; }   // behind the positions
+constexpr int pair_lds_env(int E) { return (28 * E + 15) & ~15; }          // one env's staging scratch
+constexpr int pair_lds_force(int E) { return pair_lds_scr(E) + 2 * pair_lds_env(E); }
+constexpr int pair_lds_wave(int N, int No, int E) {
+    return pair_lds_force(E) + 2 * (8 * N + 8 * No) + (8 + 8 + 4) * kWave;
+}
 constexpr int pair_lds_block(int N, int No, int E) {
     return kWavesPerBlock * pair_lds_wave(N, No, E) + 4 * (6 * kPairEnvs + 4);
 }
@@ -1831,8 +1875,11 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
     static_assert(E <= 3 * kPairHalf, "an env's positions in three passes of its half");
     static_assert(N * (M + 1) < (1 << 16) && No * M < (1 << 16), "neither half of the scan word carries");
     constexpr uint32_t abits = (1u << N) - 1u;
-    constexpr int kEnvLds = pair_lds_env(N, No, E), wstride = pair_lds_wave(N, No, E);
-    constexpr int scr_cap = 7 * E;   // words of staging scratch per env
+    static_assert(2 * E <= 256, "both envs' entities in the 8-bit fields of a staged word");
+    constexpr int wstride = pair_lds_wave(N, No, E);
+    // staged words per env (its goal rows are not staged): two lists within
+    // it fit the wave's scratch together
+    constexpr int scr_cap = 7 * E - N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & (kPairHalf - 1);
@@ -1843,13 +1890,13 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
     const int64_t eb = env_live ? b : p.B - 1;                  // (clamped: loads at valid addresses)
     const uint32_t ma = li < N ? (uint32_t)li : N - 1, mo = li < No ? (uint32_t)li : No - 1;
     unsigned char *const wave_lds = smem + wave * wstride;
-    unsigned char *const envl = wave_lds + h * kEnvLds;         // this lane's env
-    float2 *const s_buf0 = (float2 *)envl;
-    auto pos_buf = [&](int j3) { return s_buf0 + j3 * E; };     // positions before step j, by j % 3
-    float *const s_scr = (float *)(envl + roll_lds_scr(E));    // agent column pairs (sweep) / staging
-    float2 *const s_force = (float2 *)(envl + roll_lds_force(E));
-    float *const s_oxy = (float *)(s_force + N);                // obstacle column pairs [x x y y]
-    uint64_t *const s_rowa = (uint64_t *)(wave_lds + 2 * kEnvLds);
+    float2 *const s_buf0 = (float2 *)wave_lds + h * E;          // this lane's env
+    auto pos_buf = [&](int j3) { return s_buf0 + j3 * (2 * E); };   // positions before step j, by j % 3
+    uint32_t *const s_stage = (uint32_t *)(wave_lds + pair_lds_scr(E));   // the wave's staged words
+    float *const s_scr = (float *)(wave_lds + pair_lds_scr(E) + h * pair_lds_env(E));   // agent column pairs (sweep)
+    float2 *const s_force = (float2 *)(wave_lds + pair_lds_force(E)) + h * N;
+    float *const s_oxy = (float *)(wave_lds + pair_lds_force(E) + 2 * 8 * N) + h * (2 * No);   // obstacle column pairs [x x y y]
+    uint64_t *const s_rowa = (uint64_t *)(wave_lds + pair_lds_force(E) + 2 * (8 * N + 8 * No));
     uint64_t *const s_rowo = s_rowa + kWave;
     uint32_t *const s_inc = (uint32_t *)(s_rowo + kWave);
     int *const s_bc = (int *)(smem + kWavesPerBlock * wstride);   // [3][envs]: edge counts by step % 3
@@ -1900,10 +1947,10 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
         acc = make_float2(0.0f, 0.0f);
     }
     if (env_live) {
-        s_buf0[li] = s_buf0[E + li] = s_buf0[2 * E + li] = x0;
-        s_buf0[li + kPairHalf] = s_buf0[E + li + kPairHalf] = s_buf0[2 * E + li + kPairHalf] = x1;
-        if (li + 2 * kPairHalf < E)
-            s_buf0[li + 2 * kPairHalf] = s_buf0[E + li + 2 * kPairHalf] = s_buf0[2 * E + li + 2 * kPairHalf] = x2;
+        float2 *const b1 = pos_buf(1), *const b2 = pos_buf(2);
+        s_buf0[li] = b1[li] = b2[li] = x0;
+        s_buf0[li + kPairHalf] = b1[li + kPairHalf] = b2[li + kPairHalf] = x1;
+        if (li + 2 * kPairHalf < E) s_buf0[li + 2 * kPairHalf] = b1[li + 2 * kPairHalf] = b2[li + 2 * kPairHalf] = x2;
     }
     if (threadIdx.x == 0) s_red[2] = (int)(pace_v >> 24);   // the rank on the CU
     wave_sync();
@@ -2072,30 +2119,35 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
     auto emit_step = [&](const int j, const int pj3, const int cj3, const uint64_t rowa, const uint64_t rowo,
                          const int inc, const int steps_done) {
         GSM_REGION("staging");
-        // each env's list staged first (needs only its own row counts): agent
-        // rows, goal rows, obstacle rows
-        const int tot = half_last(inc, h);
-        const int a_total = tot & 0xffff, total = a_total + N + (tot >> 16);
-        int staged = -1;
-        if (env_live && total <= scr_cap) {
-            uint32_t *const scr = (uint32_t *)s_scr;
-            const uint32_t lo = (uint32_t)rowa & abits, hi = (uint32_t)(rowa >> N);
+        // both envs' rows staged first as one list (needs only their own row
+        // counts): env A's agent rows, its obstacle rows, then env B's; an env
+        // whose list exceeds its share of the scratch stages nothing
+        const int tot_a = __builtin_amdgcn_readlane(inc, kPairHalf - 1), tot_b = __builtin_amdgcn_readlane(inc, kWave - 1);
+        const int st_a = (tot_a & 0xffff) + (tot_a >> 16), st_b = (tot_b & 0xffff) + (tot_b >> 16);
+        const bool fit_a = st_a <= scr_cap, fit_b = st_b <= scr_cap;   // (wave-uniform)
+        const int in_a = fit_a ? st_a : 0, staged = in_a + (fit_b ? st_b : 0);
+        const int a_total = (h ? tot_b : tot_a) & 0xffff;
+        const bool fits = h ? fit_b : fit_a;
+        if (fits) {
+            // the lane's words less their destination: entities of env B are
+            // its own + E, and an edge skips the goal rows ahead of it
+            const uint32_t ent = (uint32_t)(h * E) * 0x101u;
+            uint32_t *const scr = s_stage + (h ? in_a : 0);
             if (agent) {
+                const uint32_t lo = (uint32_t)rowa & abits, hi = (uint32_t)(rowa >> N);
                 uint32_t *at = scr + ((inc & 0xffff) - (__popc(lo) + __popc(hi) + 1));
-                const uint32_t src = (uint32_t)li;
-                for (uint32_t w = lo; w; w &= w - 1) *at++ = src | ((uint32_t)__builtin_ctz(w) << 8);
-                *at++ = src | ((uint32_t)(N + li) << 8);
-                scr[a_total + li] = (uint32_t)(N + li) | ((uint32_t)li << 8);
-                for (uint32_t w = hi; w; w &= w - 1) *at++ = src | ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
+                const uint32_t src = ent + (uint32_t)li + ((uint32_t)(h * N) << 16);
+                for (uint32_t w = lo; w; w &= w - 1) *at++ = src + ((uint32_t)__builtin_ctz(w) << 8);
+                *at++ = src + ((uint32_t)(N + li) << 8);     // agent li -> its goal
+                for (uint32_t w = hi; w; w &= w - 1) *at++ = src + ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
             }
             if (obrow) {
                 const uint32_t olo = (uint32_t)rowo & abits, ohi = (uint32_t)(rowo >> N);
-                uint32_t *at = scr + (a_total + N + (inc >> 16) - (__popc(olo) + __popc(ohi)));
-                const uint32_t src = (uint32_t)(2 * N + li);
-                for (uint32_t w = olo; w; w &= w - 1) *at++ = src | ((uint32_t)__builtin_ctz(w) << 8);
-                for (uint32_t w = ohi; w; w &= w - 1) *at++ = src | ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
+                uint32_t *at = scr + (a_total + (inc >> 16) - (__popc(olo) + __popc(ohi)));
+                const uint32_t src = ent + (uint32_t)(2 * N + li) + ((uint32_t)((h + 1) * N) << 16);
+                for (uint32_t w = olo; w; w &= w - 1) *at++ = src + ((uint32_t)__builtin_ctz(w) << 8);
+                for (uint32_t w = ohi; w; w &= w - 1) *at++ = src + ((uint32_t)(2 * N + __builtin_ctz(w)) << 8);
             }
-            staged = total;
         }
         wave_sync();
         GSM_REGION("prefix");
@@ -2131,28 +2183,29 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
             if (b == qs.B - 1) qs.ro.eptr[qs.B] = env_off + my_cnt;
         }
         const EdgeSink out = roll_edge_sink<false>(qs, j, K);
-        // the two lists in turn, each written by all 64 lanes
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            if (wb + hh >= qs.B) break;
-            const int st = __builtin_amdgcn_readlane(staged, hh * kPairHalf);
-            const uint32_t off_lo = __builtin_amdgcn_readlane((uint32_t)env_off, hh * kPairHalf);
-            const uint32_t off_hi = __builtin_amdgcn_readlane((uint32_t)((uint64_t)env_off >> 32), hh * kPairHalf);
-            const int64_t off = (int64_t)(((uint64_t)off_hi << 32) | off_lo);
-            const float2 *const s_prev = (const float2 *)(wave_lds + hh * kEnvLds) + pj3 * E;   // positions after step j
-            if (st >= 0 && off + st <= out.cap) {
-                Lane Lw{};
-                Lw.lane = lane;
-                Lw.b = wb + hh;
-                write_staged<kN, kNo>(Lw, s_prev, (const uint32_t *)(wave_lds + hh * kEnvLds + roll_lds_scr(E)), st, off,
-                                      out);
-            } else if (h == hh) {
-                // a list longer than the scratch or than the outputs' rest:
-                // each lane its rows, every store tested
+        // The wave's lists are adjacent in the outputs (env 2w + 1's offset is
+        // env 2w's plus its count): one list from env A's offset, written by
+        // all 64 lanes, the goal rows by their agents' lanes. A list that
+        // stands alone (env A's does not fit the scratch) starts where its
+        // skips put it right.
+        if (wb < qs.B) {
+            const uint32_t off_lo = __builtin_amdgcn_readlane((uint32_t)env_off, 0);
+            const uint32_t off_hi = __builtin_amdgcn_readlane((uint32_t)((uint64_t)env_off >> 32), 0);
+            const int64_t off_a = (int64_t)(((uint64_t)off_hi << 32) | off_lo);
+            const int edges = st_a + N + (wb + 1 < qs.B ? st_b + N : 0);   // of both envs
+            const bool in_range = off_a + edges <= out.cap;                 // (a redirected slot may be smaller)
+            const float2 *const s_prev = (const float2 *)wave_lds + pj3 * (2 * E);   // positions after step j, both envs
+            if (in_range)
+                write_staged_pair<kN>(lane, s_prev, s_stage, staged, off_a + (st_a - in_a), (int32_t)((int64_t)wb * E),
+                                      agent && fits, env_off + a_total + li, (uint32_t)(h * E + N + li), out);
+            if (env_live && !(in_range && fits)) {
+                // a list longer than its share of the scratch, or the outputs'
+                // rest too short: each lane its rows, every store tested
+                const float2 *const s_own = s_prev + h * E;
                 const int32_t g0 = (int32_t)((int64_t)b * E);
                 auto put = [&](int64_t at, int32_t a, int32_t d) {
                     if (at < out.cap) {
-                        const float2 pa = s_prev[a], pd = s_prev[d];
+                        const float2 pa = s_own[a], pd = s_own[d];
                         const float dx = pa.x - pd.x, dy = pa.y - pd.y;
                         out.index[at] = g0 + a;
                         out.index[out.cap + at] = g0 + d;
@@ -2161,15 +2214,15 @@ __global__ __launch_bounds__(kBlock) GSM_PAIR_ATTR void gsm_roll_pair_kernel(Dev
                 };
                 if (agent) {
                     const uint32_t lo = (uint32_t)rowa & abits, hi = (uint32_t)(rowa >> N);
-                    int64_t o = off + ((inc & 0xffff) - (__popc(lo) + __popc(hi) + 1));
+                    int64_t o = env_off + ((inc & 0xffff) - (__popc(lo) + __popc(hi) + 1));
                     for (uint32_t w = lo; w; w &= w - 1) put(o++, li, __builtin_ctz(w));
                     put(o++, li, N + li);
                     for (uint32_t w = hi; w; w &= w - 1) put(o++, li, 2 * N + __builtin_ctz(w));
-                    put(off + a_total + li, N + li, li);
+                    put(env_off + a_total + li, N + li, li);
                 }
                 if (obrow) {
                     const uint32_t olo = (uint32_t)rowo & abits, ohi = (uint32_t)(rowo >> N);
-                    int64_t o = off + a_total + N + ((inc >> 16) - (__popc(olo) + __popc(ohi)));
+                    int64_t o = env_off + a_total + N + ((inc >> 16) - (__popc(olo) + __popc(ohi)));
                     for (uint32_t w = olo; w; w &= w - 1) put(o++, 2 * N + li, __builtin_ctz(w));
                     for (uint32_t w = ohi; w; w &= w - 1) put(o++, 2 * N + li, 2 * N + __builtin_ctz(w));
                 }
