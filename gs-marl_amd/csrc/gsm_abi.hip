@@ -1752,6 +1752,88 @@ int gsm_actor_eval_bwd(const float *g_logp, const float *g_ent, const float *x, 
     return GSM_OK;
 }
 
+// the shape limits of the critic head, before anything else is looked at
+static int critic_shape(int64_t x_row_stride, int64_t n_envs, int32_t n_agents, int32_t in_features, int32_t hidden,
+                        int32_t n_out) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (in_features < 4 || in_features > 64 || in_features % 4)
+        return fail(nullptr, GSM_EINVAL, "in_features must be a multiple of 4 in [4, 64]");
+    if (hidden != 16 && hidden != 32 && hidden != 64) return fail(nullptr, GSM_EINVAL, "hidden must be 16, 32 or 64");
+    if (n_out < 1 || n_out > 2) return fail(nullptr, GSM_EINVAL, "n_out must be 1 or 2");
+    if (n_agents < 1 || n_agents > 128 || n_envs < 0 || n_envs >= lim || n_envs * n_agents >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_agents in [1, 128], n_envs >= 0 and n_envs*n_agents < 2^31");
+    if (x_row_stride < in_features || x_row_stride % 4)
+        return fail(nullptr, GSM_EINVAL, "x_row_stride must be a multiple of 4 and >= in_features");
+    return GSM_OK;
+}
+
+static gsm::CriticParams critic_params(const float *x, int64_t x_row_stride, const int32_t *n_valid, const float *w1,
+                                       const float *b1, const float *w2, const float *b2, int64_t n_envs,
+                                       int32_t n_agents, int32_t in_features, int32_t n_out, int32_t *status) {
+    gsm::CriticParams p = {};
+    p.x = x;
+    p.x_stride = x_row_stride;
+    p.n_valid = n_valid;
+    p.w1 = w1, p.b1 = b1, p.w2 = w2, p.b2 = b2;
+    p.n_envs = n_envs;
+    p.R = n_envs * n_agents;
+    p.n_agents = n_agents;
+    p.in = in_features;
+    p.nO = n_out;
+    p.status = status;
+    return p;
+}
+
+int gsm_critic_eval(const float *x, int64_t x_row_stride, const int32_t *n_valid, const float *w1, const float *b1,
+                    const float *w2, const float *b2, const float *denorm, int64_t n_envs, int32_t n_agents,
+                    int32_t in_features, int32_t hidden, int32_t n_out, float *values, int32_t *status,
+                    void *stream) {
+    if (const int rc = critic_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_out)) return rc;
+    if (n_envs == 0) return GSM_OK;
+    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (!values) return fail(nullptr, GSM_EINVAL, "values is NULL");
+    gsm::CriticParams p = critic_params(x, x_row_stride, n_valid, w1, b1, w2, b2, n_envs, n_agents, in_features,
+                                        n_out, status);
+    p.denorm = denorm, p.values = values;
+    const hipError_t e = gsm::launch_critic_forward(p, hidden, as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_critic_eval launch");
+    return GSM_OK;
+}
+
+int gsm_critic_backward_work_floats(int32_t in_features, int32_t hidden, int32_t n_out, int64_t *n_floats) {
+    if (const int rc = critic_shape(in_features, 0, 1, in_features, hidden, n_out)) return rc;
+    if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
+    *n_floats = gsm::critic_backward_work_floats(in_features, hidden, n_out);
+    return GSM_OK;
+}
+
+int gsm_critic_eval_bwd(const float *g, const float *x, int64_t x_row_stride, const int32_t *n_valid,
+                        const float *w1, const float *b1, const float *w2, const float *b2, int64_t n_envs,
+                        int32_t n_agents, int32_t in_features, int32_t hidden, int32_t n_out, float *work,
+                        float *dw1, float *db1, float *dw2, float *db2, float *dx, int32_t *status, void *stream) {
+    if (const int rc = critic_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_out)) return rc;
+    if (!dw1 || !db1 || !dw2 || !db2) return fail(nullptr, GSM_EINVAL, "a gradient pointer is NULL");
+    hipStream_t s = as_stream(stream);
+    if (n_envs == 0) {
+        const size_t f = sizeof(float);
+        hipError_t e = hipMemsetAsync(dw2, 0, f * n_out * hidden, s);
+        if (e == hipSuccess) e = hipMemsetAsync(db2, 0, f * n_out, s);
+        if (e == hipSuccess) e = hipMemsetAsync(dw1, 0, f * hidden * 2 * in_features, s);
+        if (e == hipSuccess) e = hipMemsetAsync(db1, 0, f * hidden, s);
+        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_critic_eval_bwd memset");
+        return GSM_OK;
+    }
+    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (!g || !work) return fail(nullptr, GSM_EINVAL, "g or work is NULL");
+    if ((uintptr_t)dx % 16) return fail(nullptr, GSM_EINVAL, "dx must be 16-byte aligned");
+    gsm::CriticParams p = critic_params(x, x_row_stride, n_valid, w1, b1, w2, b2, n_envs, n_agents, in_features,
+                                        n_out, status);
+    p.g = g, p.dx = dx, p.part = work;
+    const hipError_t e = gsm::launch_critic_backward(p, hidden, dw1, db1, dw2, db2, s);
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_critic_eval_bwd launch");
+    return GSM_OK;
+}
+
 int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
             int32_t n_agents, float gamma, float gamma_lambda, float *ret, void *stream) {
     const int64_t lim = (int64_t)1 << 31;

@@ -1580,3 +1580,5 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
 
 // the actor head: gsm_actor_sample / gsm_actor_eval / gsm_actor_eval_bwd
 #include "gsm_actor.h"
+// the critic head: gsm_critic_eval / gsm_critic_eval_bwd
+#include "gsm_critic.h"

@@ -330,6 +330,27 @@ hipError_t launch_actor_forward(const ActorParams &p, int hidden, bool eval, hip
 int64_t actor_backward_work_floats(int in, int hidden, int nA);
 hipError_t launch_actor_backward(const ActorParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
                                  hipStream_t s);
+// the critic head (gsm_critic.h): what its two launchers take. R = n_envs *
+// n_agents rows; the forward writes values, the backward reads g and writes dx
+// and its partials (part, in `work`)
+struct CriticParams {
+    const float *x;
+    int64_t x_stride;
+    const int32_t *n_valid;
+    const float *w1, *b1, *w2, *b2, *denorm;
+    int64_t n_envs, R;
+    int n_agents, in, nO;
+    float *values;
+    int32_t *status;
+    const float *g;
+    float *dx, *part;
+};
+hipError_t launch_critic_forward(const CriticParams &p, int hidden, hipStream_t s);
+// floats of workspace launch_critic_backward needs: one partial (dw1, db1, dw2,
+// db2) per workgroup of its capped grid
+int64_t critic_backward_work_floats(int in, int hidden, int nO);
+hipError_t launch_critic_backward(const CriticParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
+                                  hipStream_t s);
 hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
                       float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,

@@ -8,12 +8,12 @@ from .vec_env import GpuGraphVecEnv, make_eval_env, make_train_env
 from .rollout import GraphRolloutBuffer
 from . import gnn
 from . import policy
-from .policy import ActorHead
+from .policy import ActorHead, CriticHead, PopArt
 from . import render
 from . import distributed
 
 __version__ = "0.1.0"
 __all__ = ["EnvConfig", "GpuBatchEnv", "MultiAgentEnv", "MultiAgentConstrainEnv",
            "MultiAgentGraphConstrainEnv", "make_env", "GpuGraphVecEnv", "make_train_env", "make_eval_env",
-           "GraphRolloutBuffer", "gnn", "policy", "ActorHead", "render",
+           "GraphRolloutBuffer", "gnn", "policy", "ActorHead", "CriticHead", "PopArt", "render",
            "distributed"]

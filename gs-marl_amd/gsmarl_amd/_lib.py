@@ -24,6 +24,7 @@ BATCH_BAD_INDEX, BATCH_TRUNCATED, BATCH_BAD_OFFSETS, BATCH_OUT_OF_ENV, BATCH_ASY
 CONV_SKIP, CONV_MAX_ENTITIES = 1, 288
 ACTOR_DETERMINISTIC = 1
 ACTOR_NONFINITE, ACTOR_BAD_ACTION = 1, 2
+CRITIC_NONFINITE, CRITIC_BAD_COUNT = 1, 2
 
 
 class GsmConfig(C.Structure):
@@ -126,6 +127,11 @@ SIGNATURES = {
     "gsm_actor_backward_work_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "gsm_actor_eval_bwd": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gsm_critic_eval": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, _P, _P, _P]),
+    "gsm_critic_backward_work_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "gsm_critic_eval_bwd": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gsm_gae": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "gsm_render": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

@@ -610,6 +610,70 @@ int gsm_actor_eval_bwd(const float *g_logp, const float *g_ent, const float *x, 
                        const int32_t *actions, float *work, float *dw1, float *db1, float *dw2, float *db2,
                        float *dx, int32_t *status, void *stream);
 
+/* The critic head: a centralised value readout, one or two values a row (the
+ * reward critic and the Lagrangian cost critic) from the row's features and
+ * the mean of its env's features, one launch; and its gradients. Rows r =
+ * b*n_agents + i, R = n_envs*n_agents; n_envs is any number of groups (a whole
+ * buffer of (T+1)*B stored steps is one call). x f32, row r at x +
+ * r*x_row_stride under gsm_actor_sample's rules (a view of gsm_env_conv's out
+ * works). n_valid int32 [n_envs] or NULL (every env has n_agents valid rows):
+ * the env's own agent count in a ragged batch; rows i >= n_valid[b] are
+ * padding, are never read (they may hold NaN), take no part in the pool and
+ * get 0.0 in every head. w1 f32 [hidden][2*in_features], b1 [hidden], w2
+ * [n_out][hidden], b2 [n_out]: the torch.nn.Linear layout over the
+ * concatenated input [pool_b | x_r]. denorm: device f32 [n_out][2] = (mean,
+ * std) per head, read when the kernel runs (a captured graph sees updated
+ * statistics), or NULL. Every line one correctly rounded fp32 operation, every
+ * dot product an explicit fmaf chain (the actor head's convention: the bias,
+ * then the inputs in ascending index of [pool | x]):
+ *   pool_b[j] = (x[b,0][j] + x[b,1][j] + ..  over valid i, ascending) / (float)n_b
+ *               (n_b = 0: pool = 0)
+ *   c_b[h] = chain from b1[h]: fmaf(w1[h][j], pool_b[j], acc), j ascending
+ *   h_r[h] = relu(chain continued from c_b[h]: fmaf(w1[h][F+j], x_r[j], acc))
+ *   v_r[o] = chain from b2[o]: fmaf(w2[o][h], h_r[h], acc), h ascending
+ *   values[o][r] = denorm ? v_r[o] * std_o + mean_o (a multiply, then an add)
+ *                         : v_r[o]
+ * values f32 [n_out][R], head-major: a head is a contiguous [.., n_agents]
+ * tensor. A row's result depends on its env's rows alone, bit for bit: not on
+ * where the env falls in a tile, in the grid or in the batch, so a slice of
+ * the batch gives the bits of its rows in the full batch, and a valid row of
+ * a ragged env the bits of the same rows in a dense batch of n_b agents.
+ * status (device int32 [1], OR-ed, zeroed by the caller; NULL: not wanted):
+ * GSM_CRITIC_NONFINITE: a valid row produced a non-finite v (it is written;
+ * other envs are not affected); GSM_CRITIC_BAD_COUNT: an n_valid[b] outside
+ * [0, n_agents], clamped.
+ *
+ * gsm_critic_eval_bwd: g f32 [n_out][R], the gradient with respect to the raw
+ * v (denormalisation is never differentiated: the value loss is formed on
+ * normalised targets). h, pool and c are recomputed on chip. With dv_r =
+ * g[:, r] (0 on padded rows) and F = in_features:
+ *   db2 = sum_r dv;  dW2 = sum_r dv (x) h_r
+ *   dh_r = W2^T dv_r where h_r > 0, else 0
+ *   db1 = sum_r dh;  dW1[:, F:] = sum_r dh_r (x) x_r
+ *   s_b = sum_{i valid} dh_{b,i} (ascending);  dW1[:, :F] = sum_b s_b (x) pool_b
+ *   dpool_b = W1[:, :F]^T s_b;  dx_r = W1[:, F:]^T dh_r + dpool_b / n_b
+ * (padded rows: dx = 0). dw1, db1, dw2, db2 in the weights' layouts; dx f32
+ * [R][in_features], 16-byte aligned, or NULL (not wanted). work: device f32,
+ * gsm_critic_backward_work_floats of them (one partial per workgroup of a
+ * capped grid). No float atomics; the summation order depends on the shape
+ * alone, so the gradients are bitwise reproducible. With n_envs == 0 the
+ * weight gradients are zeros and nothing else is launched.
+ * Shape limits (GSM_EINVAL, checked first): in_features a multiple of 4 in
+ * [4, 64]; hidden 16, 32 or 64; n_out 1 or 2; n_agents in [1, 128];
+ * n_envs*n_agents < 2^31; x_row_stride as for the actor head. Every shape
+ * inside them launches. Stateless; asynchronous on `stream`. */
+#define GSM_CRITIC_NONFINITE 1 /* status: a valid row had a non-finite value     */
+#define GSM_CRITIC_BAD_COUNT 2 /* status: an n_valid[b] outside [0, n_agents]    */
+int gsm_critic_eval(const float *x, int64_t x_row_stride, const int32_t *n_valid, const float *w1, const float *b1,
+                    const float *w2, const float *b2, const float *denorm, int64_t n_envs, int32_t n_agents,
+                    int32_t in_features, int32_t hidden, int32_t n_out, float *values, int32_t *status,
+                    void *stream);
+int gsm_critic_backward_work_floats(int32_t in_features, int32_t hidden, int32_t n_out, int64_t *n_floats);
+int gsm_critic_eval_bwd(const float *g, const float *x, int64_t x_row_stride, const int32_t *n_valid,
+                        const float *w1, const float *b1, const float *w2, const float *b2, int64_t n_envs,
+                        int32_t n_agents, int32_t in_features, int32_t hidden, int32_t n_out, float *work,
+                        float *dw1, float *db1, float *dw2, float *db2, float *dx, int32_t *status, void *stream);
+
 /* GAE returns of a stored episode of T = n_steps actions in one launch, with
  * BN = [n_envs][n_agents]: reward f32 [T]BN (entry t: the reward of action t),
  * value f32 [T+1]BN, done uint8 [T+1][n_envs] (slot t+1: action t ended the
