@@ -3,8 +3,9 @@
 // Host-only bookkeeping: validate the config, derive the fp32 constants the
 // kernels use (same fp32 operations as oracle/batch_ref.py:Spec), borrow the
 // caller's device buffers, launch, and optionally capture whole multi-step
-// rollouts into a HIP graph. No allocation and no synchronisation happens in
-// gsm_step / gsm_reset / gsm_observe.
+// rollouts: a per-step chain into a HIP graph, a fused rollout as one stored
+// kernel launch (planned by gsm_roll_plan.h). No allocation and no
+// synchronisation happens in gsm_step / gsm_reset / gsm_observe.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,6 +21,22 @@
 #include "gsm.h"
 #include "gsm_internal.h"
 #include "gsm_philox.h"
+#include "gsm_roll_plan.h"
+
+namespace {
+// u64 words between the chunk sums of the segmented rollout's one-hop prefix
+// (gsm_device.h roll_prefix): each on a 64-byte line of its own
+constexpr int kCsumStride = 8;
+// what gsm_roll_plan.h takes from gsm_internal.h
+constexpr gsm::RollConsts kRollConsts{gsm::kWave,
+                                      gsm::kWavesPerBlock,
+                                      gsm::kPrefixChunk,
+                                      kCsumStride,
+                                      gsm::kRollMaxSteps,
+                                      (size_t)gsm::kPaceKeys * gsm::kPaceStride,
+                                      (size_t)gsm::kEpochReps * gsm::kEpochStride};
+gsm::Knobs read_knobs() { return gsm::read_knobs(getenv, gsm::kRaggedRollMaxDepth); }
+}  // namespace
 
 struct gsm_handle {
     gsm_config cfg;
@@ -41,28 +58,25 @@ struct gsm_handle {
         int steps = 0;
         int kern = 0;
         bool each = false;
-        uint64_t *gran = nullptr;     // fused rollout: a 16-byte header, then the edge-sum granules
-        void *gran_base = nullptr;    // its allocation (gran_malloc: the granules end at its end)
-        // one-env-per-wave segmented rollout: the chunk sums of its one-hop
-        // CSR prefix (two halves of csum_half words inside gran) and its pace
-        // counters (two halves of kPaceKeys x kPaceStride u32; nullptr: pacing
-        // off); a launch uses half (launches & 1) and zeroes the other for the
-        // slot's next launch
-        uint64_t *csum = nullptr;
-        int64_t csum_half = 0;
-        uint32_t *pace = nullptr;
-        uint32_t launches = 0;
-        uint32_t last_epoch = 0xffffffffu;   // the epoch of the slot's previous launch
-        bool roll = false;            // the graph is one rollout launch
-        // A rollout graph without timing events is one kernel node: launched
-        // directly (the same kernel, grid and arguments) — a plain dispatch
-        // costs the host less than a graph launch; the graph is kept for
-        // gsm_graph_info and as the record of what runs.
-        bool direct = false;
+        // A rollout slot holds no graph: it is one stored kernel launch (fn,
+        // grid, block, lds, args) — a plain dispatch costs the host less than a
+        // graph launch, and every launch takes arguments of its own
+        // (gsm_graph_launch).
+        bool roll = false;
         const void *fn = nullptr;
         dim3 grid, block;
         unsigned lds = 0;
         gsm::DevParams args;
+        uint64_t *gran = nullptr;     // its granules' used bytes, laid out by `lay`
+        void *gran_base = nullptr;    // their allocation (gran_malloc: the used bytes end at its end)
+        gsm::GranLayout lay{};
+        // the one-hop rollouts' chunk sums and pace counters (paced: pacing
+        // on) come in two halves: a launch uses half (launches & 1) and
+        // zeroes the other for the slot's next launch
+        bool paced = false;
+        uint32_t launches = 0;
+        uint32_t last_epoch = 0xffffffffu;   // the epoch of the slot's previous launch
+        bool captured() const { return exec != nullptr || roll; }
     } slots[GSM_GRAPH_SLOTS];
     uint32_t *roll_status = nullptr;  // fused rollout: a bounded wait gave up (sticky until read)
     void *edge_scratch = nullptr;     // fused rollout in the bound buffers: edges of all but the last step
@@ -74,14 +88,11 @@ struct gsm_handle {
     hipStream_t roll_stream = nullptr;
     bool roll_launched = false;
     hipEvent_t roll_done = nullptr;   // recorded behind every rollout-slot launch
-    uint64_t *eager_csum = nullptr;   // the eager one-launch step's chunk-sum halves (inside eager_gran)
-    int64_t eager_csum_half = 0;
-    uint32_t *eager_epoch = nullptr;  // its device-side epoch (inside eager_gran)
     // gsm_step as a one-step rollout launch (step + its edges in one kernel):
     // -1 not yet decided for this config, 0 no (two launches), 1 yes
     int eager_roll = -1;
-    uint64_t *eager_gran = nullptr;   // its granules (K = 1)
-    uint64_t *eager_gran_end = nullptr;
+    uint64_t *eager_gran = nullptr;   // its granules' used bytes (K = 1), laid out by eager_lay
+    gsm::GranLayout eager_lay{};
     void *eager_base = nullptr;       // their allocation
 };
 
@@ -138,16 +149,8 @@ int update_block_order(gsm_handle *h, hipStream_t s) {
     // cost units per env and step: polygon/line a + b N, navigation c + d N,
     // the C4 rollout's best of a scan (tools/gpu.sh envsweep,
     // GSM_PLACE_MODEL="a,b,c,d" overrides)
-    int64_t ma = 200, mb = 20, mc = 10, md = 3;
-    if (const char *ev = getenv("GSM_PLACE_MODEL")) {
-        long long x[4];
-        if (sscanf(ev, "%lld,%lld,%lld,%lld", &x[0], &x[1], &x[2], &x[3]) == 4) {
-            ma = x[0];
-            mb = x[1];
-            mc = x[2];
-            md = x[3];
-        }
-    }
+    const gsm::Knobs knobs = read_knobs();
+    const int64_t ma = knobs.model[0], mb = knobs.model[1], mc = knobs.model[2], md = knobs.model[3];
     for (int b = 0; b < p.B; ++b) {
         const int64_t gid = p.env_base + b;
         const gsm::Philox4 x = gsm::philox4x32_10(0u, 0u, (uint32_t)gid, gsm::kTagShape, p.seed_lo, p.seed_hi);
@@ -170,12 +173,11 @@ int update_block_order(gsm_handle *h, hipStream_t s) {
     // writing back its own partial copy of the line. GSM_PLACE_XCD=0: one cost
     // order over the whole grid (round 4).
     int n_cu = 0, dev = 0;
-    const char *px = getenv("GSM_PLACE_XCD");
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         n_cu = 0;
     const int S = 4 * n_cu, SX = S / kXcds;
-    if (!(px && atoi(px) == 0) && S > 0 && S % kXcds == 0 && W % S == 0) {
+    if (knobs.place_xcd && S > 0 && S % kXcds == 0 && W % S == 0) {
         const int R = W / S, WX = W / kXcds;
         std::vector<int32_t> blk(WX);
         for (int x = 0; x < kXcds; ++x) {
@@ -427,9 +429,6 @@ int redirect(gsm_handle *h, gsm::DevParams *p, const gsm_outputs *o) {
 
 uint32_t next_launch_epoch();
 hipError_t clear_status(gsm_handle *h);
-// u64 words between the chunk sums of the segmented rollout's one-hop prefix
-// (gsm_device.h roll_prefix): each on a 64-byte line of its own
-constexpr int kCsumStride = 8;
 // a launch epoch other than `last` (the previous launch of the same granules:
 // the process-wide counter wraps after 2^20 launches, and an idle slot's
 // granules still carry its last launch's tags), recorded as the new last
@@ -463,6 +462,55 @@ hipError_t gran_malloc(void **base, uint64_t **gran, size_t bytes) {
     return hipSuccess;
 }
 
+// the address of a GranLayout offset (gsm_roll_plan.h) in a granule
+// allocation's used bytes: the only arithmetic on granule memory
+template <typename T>
+T *gran_at(uint64_t *gran, size_t off) {
+    return reinterpret_cast<T *>(reinterpret_cast<char *>(gran) + off);
+}
+
+// the status word of the rollouts' bounded waits, allocated and cleared once
+int ensure_status(gsm_handle *h) {
+    if (h->roll_status) return GSM_OK;
+    hipError_t e = hipMalloc(&h->roll_status, 16);
+    if (e == hipSuccess) e = clear_status(h);
+    if (e == hipSuccess) return GSM_OK;
+    h->roll_status = nullptr;
+    return hip_fail(h, e, "hipMalloc (rollout status)");
+}
+
+// the library's own stream: granule init and graph upload at capture
+int ensure_cap_stream(gsm_handle *h) {
+    if (h->cap_stream) return GSM_OK;
+    const hipError_t e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
+    return e == hipSuccess ? GSM_OK : hip_fail(h, e, "hipStreamCreate");
+}
+
+// what one residency round of a rollout kernel holds: workgroups per CU, CUs
+hipError_t query_round(const gsm::RollForm &form, int *per_cu, int *n_cu) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, form.fn, form.threads, form.lds);
+    return e;
+}
+
+// a rollout's outputs all in the launch's bound (or redirected) buffers
+gsm::DevParams::RollOut bound_roll_out(const gsm::DevParams &p) {
+    gsm::DevParams::RollOut ro{};
+    ro.nf = p.node_feat;
+    ro.rew = p.reward;
+    ro.cost = p.cost;
+    ro.done = p.done;
+    ro.ecount = p.edge_count;
+    ro.eptr = p.edge_ptr;
+    ro.eidx = p.edge_index;
+    ro.eattr = p.edge_attr;
+    ro.cap = p.edge_capacity;
+    ro.asg = p.assign;
+    return ro;
+}
+
 // gsm_step as ONE launch: the config's fused rollout kernel with K = 1 (the
 // step, then its edges at the CSR offset of the in-launch prefix) instead of
 // the step kernel + the emit kernel — the same operations, so the same outputs
@@ -485,47 +533,34 @@ int eager_setup(gsm_handle *h) {
     h->eager_roll = 0;
     const gsm::RollForm form = gsm::roll_seg_eager_form(p);
     if (!form.fn) return GSM_OK;
-    const char *ev = getenv("GSM_EAGER_ONE_LAUNCH");
-    if (ev && *ev && atoi(ev) == 0) return GSM_OK;
-    const int nb = (p.B + form.envs - 1) / form.envs;
-    const size_t nc = ((size_t)nb + gsm::kPrefixChunk - 1) / gsm::kPrefixChunk;
-    if (nc > (size_t)gsm::kWave) return GSM_OK;   // roll_prefix: one chunk sum per lane
-    int dev = 0, per_cu = 0, n_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, form.fn, form.threads, form.lds);
+    if (!read_knobs().eager_one_launch) return GSM_OK;
+    // one step, per-workgroup hand-off: the workgroups' aggregates, two halves
+    // of chunk sums, no pacing, then the device-side epoch replicas
+    const gsm::RollShape shape = gsm::roll_shape(kRollConsts, 1, (p.B + form.envs - 1) / form.envs, false, true);
+    int per_cu = 0, n_cu = 0;
+    hipError_t e = query_round(form, &per_cu, &n_cu);
     if (e != hipSuccess) return hip_fail(h, e, "occupancy query (eager rollout)");
-    if ((int64_t)per_cu * n_cu < nb) return GSM_OK;
-    // the workgroups' aggregates and two halves of chunk sums, then the
-    // device-side epoch replicas
-    const size_t words = (size_t)nb + 2 * nc * kCsumStride;
-    const size_t epoch_bytes = (size_t)gsm::kEpochReps * gsm::kEpochStride * sizeof(uint32_t);
-    const size_t bytes = 16 + words * sizeof(uint64_t) + epoch_bytes;
+    if (gsm::roll_limits(kRollConsts, shape, 1, 0, per_cu, n_cu) != gsm::RollLimit::kNone) return GSM_OK;
+    const gsm::GranLayout lay = gsm::gran_layout(kRollConsts, shape);
     if (h->eager_base) {   // (a retried setup)
         (void)hipFree(h->eager_base);
         h->eager_base = nullptr;
         h->eager_gran = nullptr;
     }
-    e = gran_malloc(&h->eager_base, &h->eager_gran, bytes);
-    h->eager_gran_end = h->eager_gran ? (uint64_t *)((char *)h->eager_gran + bytes) : nullptr;
-    h->eager_csum = h->eager_gran ? h->eager_gran + 2 + nb : nullptr;
-    h->eager_csum_half = (int64_t)(nc * kCsumStride);
-    h->eager_epoch = h->eager_gran ? (uint32_t *)((char *)h->eager_gran + bytes - epoch_bytes) : nullptr;
-    if (e != hipSuccess) { h->eager_gran = nullptr; return hip_fail(h, e, "hipMalloc (eager granules)"); }
-    e = gsm::launch_granule_init(h->eager_gran, bytes, 0u, nullptr);
+    e = gran_malloc(&h->eager_base, &h->eager_gran, lay.bytes);
+    if (e != hipSuccess) return hip_fail(h, e, "hipMalloc (eager granules)");
+    h->eager_lay = lay;
+    e = gsm::launch_granule_init(h->eager_gran, lay.bytes, 0u, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e == hipSuccess) {   // the first epoch: a fresh one of the process-wide sequence, in every replica
-        std::vector<uint32_t> ep((size_t)gsm::kEpochReps * gsm::kEpochStride, 0u);
+        std::vector<uint32_t> ep(lay.epoch.bytes / sizeof(uint32_t), 0u);
         const uint32_t e0 = next_launch_epoch();
         for (int r = 0; r < gsm::kEpochReps; ++r) ep[(size_t)r * gsm::kEpochStride] = e0;
-        e = hipMemcpy(h->eager_epoch, ep.data(), epoch_bytes, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess && !h->roll_status) {
-        e = hipMalloc(&h->roll_status, 16);
-        if (e == hipSuccess) e = clear_status(h);
-        if (e != hipSuccess) h->roll_status = nullptr;
+        e = hipMemcpy(gran_at<uint32_t>(h->eager_gran, lay.epoch.off), ep.data(), lay.epoch.bytes,
+                      hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return hip_fail(h, e, "eager rollout setup");
+    if (const int rc = ensure_status(h)) return rc;
     h->eager_roll = 1;
     return GSM_OK;
 }
@@ -543,19 +578,24 @@ int launch_step_roll(gsm_handle *h, gsm::DevParams p, hipStream_t s) {
     const gsm::RollForm form = gsm::roll_seg_eager_form(p);   // (the action format may differ per call)
     if (!form.fn) return kEagerIneligible;
     const int nb = (p.B + form.envs - 1) / form.envs;
+    const gsm::GranLayout &lay = h->eager_lay;
     // the step's outputs: the bound (or redirected) buffers, its edges too
-    p.ro = gsm::DevParams::RollOut{p.node_feat, p.reward, p.cost, p.done, p.edge_count, p.edge_ptr, p.edge_index,
-                                   p.edge_attr, 0, 0, 0, 0, 0, 0, 0, p.edge_capacity, nullptr, nullptr, p.assign, 0};
+    p.ro = bound_roll_out(p);
     // (one step: no pacing; per-workgroup hand-off: no xW / xNG; the epoch
     // field unused)
-    p.roll = gsm::DevParams::Roll{(const char *)p.actions, 0, 1, 0, 1, 0, 0, 0, 0, 0, h->eager_gran + 2,
-                                  h->roll_status, 0u};
+    gsm::DevParams::Roll r{};
+    r.actions = (const char *)p.actions;
+    r.n_actions = 1;
+    r.K = 1;
+    r.gran = gran_at<uint64_t>(h->eager_gran, lay.granules.off);
+    r.status = h->roll_status;
     // (the halves in a fixed order: the kernel picks by the epoch's parity)
-    p.roll.csum = h->eager_csum;
-    p.roll.csum_next = h->eager_csum + h->eager_csum_half;
-    p.roll.csum_stride = kCsumStride;
-    p.roll.gran_end = h->eager_gran_end;
-    p.roll.dev_epoch = h->eager_epoch;
+    r.csum = gran_at<uint64_t>(h->eager_gran, lay.csum[0].off);
+    r.csum_next = gran_at<uint64_t>(h->eager_gran, lay.csum[1].off);
+    r.csum_stride = kCsumStride;
+    r.gran_end = gran_at<uint64_t>(h->eager_gran, lay.bytes);
+    r.dev_epoch = gran_at<uint32_t>(h->eager_gran, lay.epoch.off);
+    p.roll = r;
     void *args[] = {&p};
     const hipError_t e = hipLaunchKernel(form.fn, dim3(nb), dim3(form.threads), args, (unsigned)form.lds, s);
     if (e != hipSuccess) return hip_fail(h, e, "hipLaunchKernel (one-step rollout)");
@@ -594,12 +634,10 @@ void drop_slot(gsm_handle::Slot &s) {
     if (s.gran_base) (void)hipFree(s.gran_base);
     s.gran_base = nullptr;
     s.gran = nullptr;
-    s.csum = nullptr;
-    s.csum_half = 0;
-    s.pace = nullptr;
+    s.lay = gsm::GranLayout{};
+    s.paced = false;
     s.launches = 0;
     s.roll = false;
-    s.direct = false;
     s.fn = nullptr;
     s.exec = nullptr;
     s.graph = nullptr;
@@ -833,296 +871,245 @@ int gsm_graph_capture_into(gsm_handle *h, int32_t slot, const void *actions, int
     return capture_impl(h, slot, actions, stride, n_actions, n_steps, action_fmt, 0, per_step);
 }
 
-
-
-// Fused rollout graph (GSM_GRAPH_ROLL): ONE gsm_roll_seg_kernel /
-// gsm_roll_tile_kernel / gsm_roll_ragged_kernel launch for all n_steps steps
-// and all their edges (a tail after the loop emits the last ones; that launch
-// also advances the granule epoch). Every output equals the per-step chain's.
-// The ragged rollout packs each step's edges `depth` steps late
-// (GSM_ROLL_DEPTH, default 4, 2..kRaggedRollMaxDepth).
-static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_t stride, int32_t n_actions,
-                        int32_t n_steps, int action_fmt, int flags, const gsm_outputs *per_step, bool fallback) {
-    // every caller checks these first; repeated so that no path reaches the
-    // slot or the bound buffers without them
-    if (!h) return fail(nullptr, GSM_EINVAL, "handle is NULL");
-    if (!h->bound) return fail(h, GSM_ESTATE, "gsm_bind has not been called");
-    if (bad_slot(slot)) return fail(h, GSM_EINVAL, "bad graph slot");
-    if (flags & ~(GSM_GRAPH_ROLL | GSM_GRAPH_TIME_ENDS))
-        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL combines with GSM_GRAPH_TIME_ENDS only");
-    if (!actions || n_actions < 1 || stride < 0) return fail(h, GSM_EINVAL, "bad capture arguments");
-    // the rollout kernels address the action rows with 32-bit byte offsets
-    if ((uint64_t)n_actions * (uint64_t)stride >= ((uint64_t)1 << 32)) {
-        if (fallback) return kRollIneligible;
-        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: the action rows must span < 4 GiB");
+// Step k's outputs at base + k * stride, from a rollout buffer's slots:
+// *regular where every redirected field sits at a constant stride. p ends up
+// describing the last slot (redirect validates each one).
+static int roll_out_slots(gsm_handle *h, const gsm_outputs *per_step, int n_steps, bool ragged, gsm::DevParams *p,
+                          gsm::DevParams::RollOut *ro, bool *regular) {
+    int64_t cost_s = 0;
+    bool ok = slot_field(per_step, n_steps, &gsm_outputs::node_feat, &ro->nf, &ro->nf_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::reward, &ro->rew, &ro->rc_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::cost, &ro->cost, &cost_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::done, &ro->done, &ro->done_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::edge_count, &ro->ecount, &ro->ec_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::edge_ptr, &ro->eptr, &ro->ep_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::edge_index, &ro->eidx, &ro->ei_s) &&
+              slot_field(per_step, n_steps, &gsm_outputs::edge_attr, &ro->eattr, &ro->ea_s) &&
+              cost_s == ro->rc_s && (ragged ? slot_field(per_step, n_steps, &gsm_outputs::assign, &ro->asg, &ro->as_s)
+                                            : !per_step[0].assign);
+    for (int j = 0; ok && j < n_steps; ++j) {
+        const int rc = redirect(h, p, &per_step[j]);
+        if (rc) return rc;
+        ok = !per_step[0].edge_index || per_step[j].edge_capacity == per_step[0].edge_capacity;
     }
-    if (n_steps < 1) return fail(h, GSM_EINVAL, "n_steps must be >= 1");
-    if (action_fmt < GSM_ACT_ONEHOT || action_fmt > GSM_ACT_CONT) return fail(h, GSM_EINVAL, "bad action_fmt");
-    gsm::DevParams p = h->dp;
+    if (ok && per_step[0].edge_index) ro->cap = per_step[0].edge_capacity;
+    *regular = ok;
+    return GSM_OK;
+}
+
+// What a rollout capture decides before it acquires anything.
+struct RollPlan {
+    const char *refused = nullptr;   // why this is not one rollout launch (then nothing else is set)
+    gsm::Knobs knobs;
+    gsm::RollForm form{};
+    gsm::DevParams p;                // the launch's arguments but for p.roll (the outputs: the last slot's)
+    gsm::RollShape shape{};
+    gsm::GranLayout lay{};
+    int n_cu = 0;
+    int depth = 0;                   // ragged: edges packed this many steps late
+    size_t slab_bytes = 0;           // ragged: the env slabs it needs
+};
+
+static int plan_roll(gsm_handle *h, int64_t stride, int32_t n_actions, int32_t n_steps, int action_fmt,
+                     const gsm_outputs *per_step, RollPlan *plan) {
+    plan->knobs = read_knobs();
+    gsm::DevParams &p = plan->p;
+    p = h->dp;
     p.mode = GSM_MODE_STEP;
     p.action_fmt = action_fmt;
     p.env_mask = nullptr;
     p.reseed = 0;
     const bool tile = p.path == gsm::kPathTile, ragged = p.path == gsm::kPathRagged;
     const bool slots = per_step != nullptr;
-    // pacing: the rank offset in quarter steps (GSM_ROLL_PACE, default 2;
-    // 0 = no pacing: an A/B knob, outputs are the same either way)
-    int pace_q = 0;
-    bool pace_on = true;
-    if (const char *ev = getenv("GSM_ROLL_PACE")) {
-        if (!strcmp(ev, "off"))
-            pace_on = false;
-        else
-            pace_q = std::max(0, atoi(ev));
-    }
     // what the launch runs: the kernel, its workgroup, envs per workgroup and
     // LDS. The segmented path chooses among several kernels by the launch's
     // arguments (gsm_seg_kernels.hip pick_roll_seg); of those it depends on,
     // only nf_full changes below (redirect, rollout buffers only), and a
     // rollout buffer's choice does not depend on it
-    const gsm::RollForm form =
-        tile ? gsm::RollForm{gsm::roll_tile_kernel_fn(p, slots), gsm::block_threads(p), 1,
-                             gsm::roll_tile_kernel_lds(p), false}
-             : ragged ? gsm::RollForm{gsm::roll_ragged_kernel_fn(p, slots), gsm::block_threads(p),
-                                      gsm::kWavesPerBlock, gsm::roll_ragged_kernel_lds(p), true}
-                      : gsm::roll_seg_form(p, slots, pace_on);
-    if (!form.fn && fallback) return kRollIneligible;
-    if (!form.fn) return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: no fused rollout kernel for this config "
-                                             "(segmented path with a compiled shape, tile path with the "
-                                             "symmetric sweep, or a ragged batch)");
+    plan->form = tile ? gsm::RollForm{gsm::roll_tile_kernel_fn(p, slots), gsm::block_threads(p), 1,
+                                      gsm::roll_tile_kernel_lds(p), false}
+                      : ragged ? gsm::RollForm{gsm::roll_ragged_kernel_fn(p, slots), gsm::block_threads(p),
+                                               gsm::kWavesPerBlock, gsm::roll_ragged_kernel_lds(p), true}
+                               : gsm::roll_seg_form(p, slots, plan->knobs.pace_on);
+    const gsm::RollForm &form = plan->form;
+    if (!form.fn) {
+        plan->refused = "GSM_GRAPH_ROLL: no fused rollout kernel for this config (segmented path with a compiled "
+                        "shape, tile path with the symmetric sweep, or a ragged batch)";
+        return GSM_OK;
+    }
     // step k's outputs at base + k * stride (a rollout buffer's slots) or all
     // in the bound buffers
-    gsm::DevParams::RollOut ro{p.node_feat, p.reward, p.cost, p.done, p.edge_count, p.edge_ptr, p.edge_index,
-                               p.edge_attr, 0, 0, 0, 0, 0, 0, 0, p.edge_capacity, nullptr, nullptr, p.assign, 0};
+    p.ro = bound_roll_out(p);
     if (per_step) {
-        int64_t cost_s = 0;
-        bool ok = slot_field(per_step, n_steps, &gsm_outputs::node_feat, &ro.nf, &ro.nf_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::reward, &ro.rew, &ro.rc_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::cost, &ro.cost, &cost_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::done, &ro.done, &ro.done_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::edge_count, &ro.ecount, &ro.ec_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::edge_ptr, &ro.eptr, &ro.ep_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::edge_index, &ro.eidx, &ro.ei_s) &&
-                  slot_field(per_step, n_steps, &gsm_outputs::edge_attr, &ro.eattr, &ro.ea_s) &&
-                  cost_s == ro.rc_s && (ragged ? slot_field(per_step, n_steps, &gsm_outputs::assign, &ro.asg, &ro.as_s)
-                                               : !per_step[0].assign);
-        for (int j = 0; ok && j < n_steps; ++j) {
-            const int rc = redirect(h, &p, &per_step[j]);   // validates the slot
-            if (rc) return rc;
-            ok = !per_step[0].edge_index || per_step[j].edge_capacity == per_step[0].edge_capacity;
+        bool regular = false;
+        const int rc = roll_out_slots(h, per_step, n_steps, ragged, &p, &p.ro, &regular);
+        if (rc) return rc;
+        if (!regular) {
+            plan->refused = "GSM_GRAPH_ROLL: per-step outputs must sit at constant strides";
+            return GSM_OK;
         }
-        if (!ok) {
-            if (fallback) return kRollIneligible;
-            return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: per-step outputs must sit at constant strides");
-        }
-        if (per_step[0].edge_index) ro.cap = per_step[0].edge_capacity;
-        // p now describes the last slot: the final emit launch writes it
     }
-    // segmented / ragged rollout: one env per wave whatever the config's G (4 per workgroup), two
-    // per wave (8, gsm_roll_pair_kernel), or four small envs per wave (16 per workgroup)
-    const int nb = (p.B + form.envs - 1) / form.envs;
-    // every workgroup resident at once (one residency round; a workgroup only
-    // waits on lower-numbered ones, so this is for speed, not for progress)
-    int dev = 0, per_cu = 0, n_cu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, form.fn, form.threads, form.lds);
+    // segmented / ragged rollout: one env per wave whatever the config's G (4
+    // per workgroup), two per wave (8, gsm_roll_pair_kernel), or four small
+    // envs per wave (16 per workgroup); per-wave granules (Xfer) for the
+    // ragged and packed small envs, the other segmented shapes and the tile
+    // path look back per workgroup
+    plan->shape = gsm::roll_shape(kRollConsts, n_steps, (p.B + form.envs - 1) / form.envs, form.per_wave);
+    if (ragged) plan->shape.place_words = gsm::PlaceArea::words(plan->shape.xW);
+    int per_cu = 0;
+    const hipError_t e = query_round(form, &per_cu, &plan->n_cu);
     if (e != hipSuccess) return hip_fail(h, e, "occupancy query");
-    if ((int64_t)per_cu * n_cu < nb) {
-        if (fallback) return kRollIneligible;
-        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: the batch exceeds one residency round of the rollout kernel");
+    const gsm::RollLimit limit =
+        gsm::roll_limits(kRollConsts, plan->shape, (uint64_t)n_actions, (uint64_t)stride, per_cu, plan->n_cu);
+    if (limit != gsm::RollLimit::kNone) {
+        plan->refused = gsm::roll_limit_text(limit);
+        return GSM_OK;
     }
-    const int K = n_steps;
-    // granule tags carry the step in 12 bits; checked before the slot's
-    // graph is dropped
-    if (K > gsm::kRollMaxSteps) {
-        if (fallback) return kRollIneligible;
-        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: n_steps must be <= 4094");
-    }
-    // ragged and packed small envs: per-wave granules, groups of 64 waves (at
-    // most 128 groups: one residency round holds <= 8192 waves); ragged: edges
-    // packed `depth` steps late
-    const int xW = nb * gsm::kWavesPerBlock, xNG = (xW + gsm::kWave - 1) / gsm::kWave;
-    // per-wave granules (Xfer): ragged and packed small envs; the other
-    // segmented shapes and the tile path look back per workgroup
-    const bool per_wave = form.per_wave;
-    if (per_wave && xNG > 2 * gsm::kWave) {
-        if (fallback) return kRollIneligible;
-        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: more than 8192 envs in one rollout launch");
-    }
-    int depth = 0;
+    plan->lay = gsm::gran_layout(kRollConsts, plan->shape);
     if (ragged) {
-        depth = 4;
-        if (const char *ev = getenv("GSM_ROLL_DEPTH")) depth = atoi(ev);
-        depth = std::min(std::max(depth, 2), gsm::kRaggedRollMaxDepth);
         // the env slabs of depth + 1 steps (each env's edges at a fixed stride:
         // max_edges_per_env + 1 words, then as many distances)
-        const size_t need = (size_t)(depth + 1) * p.B * 8 * ((size_t)h->sz.max_edges_per_env + 1);
-        if (h->slab_bytes < need) {
-            // a deeper ring than before: the slabs are re-allocated, and every
-            // earlier ragged rollout slot is re-pointed at them (a slab holds
-            // only the edges in flight within one launch, so nothing in the
-            // old one outlives its launches: drained first)
-            void *fresh = nullptr;
-            e = hipMalloc(&fresh, need);
-            if (e != hipSuccess) {
-                if (fallback) return kRollIneligible;
-                return hip_fail(h, e, "hipMalloc (rollout edge slabs)");
-            }
-            if (h->slab) {
-                e = hipDeviceSynchronize();
-                if (e != hipSuccess) { (void)hipFree(fresh); return hip_fail(h, e, "hipDeviceSynchronize (slabs)"); }
-                (void)hipFree(h->slab);
-            }
-            for (auto &o : h->slots)
-                if (o.roll && o.args.path == gsm::kPathRagged) {
-                    o.args.roll.slab = (int32_t *)fresh;
-                    o.args.roll.slab_end = (int32_t *)((char *)fresh + need);
-                }
-            h->slab = fresh;
-            h->slab_bytes = need;
+        plan->depth = plan->knobs.depth;
+        plan->slab_bytes = (size_t)(plan->depth + 1) * p.B * 8 * ((size_t)h->sz.max_edges_per_env + 1);
+    }
+    return GSM_OK;
+}
+
+// A deeper ring than before: the slabs are replaced by `fresh`, and every
+// earlier ragged rollout slot is re-pointed at them (a slab holds only the
+// edges in flight within one launch, so nothing in the old one outlives its
+// launches: drained first).
+static int replace_slabs(gsm_handle *h, void *fresh, size_t bytes) {
+    if (h->slab) {
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void)hipFree(fresh);
+            return hip_fail(h, e, "hipDeviceSynchronize (slabs)");
         }
+        (void)hipFree(h->slab);
     }
-    if (!h->roll_status) {
-        e = hipMalloc(&h->roll_status, 16);
-        if (e == hipSuccess) e = clear_status(h);
-        if (e != hipSuccess) { h->roll_status = nullptr; return hip_fail(h, e, "hipMalloc (rollout status)"); }
+    for (auto &o : h->slots)
+        if (o.roll && o.args.path == gsm::kPathRagged) {
+            o.args.roll.slab = (int32_t *)fresh;
+            o.args.roll.slab_end = (int32_t *)((char *)fresh + bytes);
+        }
+    h->slab = fresh;
+    h->slab_bytes = bytes;
+    return GSM_OK;
+}
+
+// Fused rollout (GSM_GRAPH_ROLL): ONE gsm_roll_seg_kernel /
+// gsm_roll_tile_kernel / gsm_roll_ragged_kernel launch for all n_steps steps
+// and all their edges (a tail after the loop emits the last ones; that launch
+// also advances the granule epoch). Every output equals the per-step chain's.
+// The slot stores the launch (kernel, grid, arguments), not a graph:
+// gsm_graph_launch completes the arguments and dispatches it.
+static int capture_roll(gsm_handle *h, int32_t slot, const void *actions, int64_t stride, int32_t n_actions,
+                        int32_t n_steps, int action_fmt, int flags, const gsm_outputs *per_step, bool fallback) {
+    // 1. the arguments. Every caller checks the first three; repeated so that
+    // no path reaches the slot or the bound buffers without them
+    if (!h) return fail(nullptr, GSM_EINVAL, "handle is NULL");
+    if (!h->bound) return fail(h, GSM_ESTATE, "gsm_bind has not been called");
+    if (bad_slot(slot)) return fail(h, GSM_EINVAL, "bad graph slot");
+    if (flags & ~(GSM_GRAPH_ROLL | GSM_GRAPH_TIME_ENDS))
+        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL combines with GSM_GRAPH_TIME_ENDS only");
+    if (!actions || n_actions < 1 || stride < 0) return fail(h, GSM_EINVAL, "bad capture arguments");
+    if (n_steps < 1) return fail(h, GSM_EINVAL, "n_steps must be >= 1");
+    if (action_fmt < GSM_ACT_ONEHOT || action_fmt > GSM_ACT_CONT) return fail(h, GSM_EINVAL, "bad action_fmt");
+
+    // 2. the plan: kernel, outputs, limits, granule layout. Where this cannot
+    // be one rollout launch, a caller that can fall back takes the per-step
+    // chain (which needs none of what follows), any other gets the reason
+    RollPlan plan;
+    if (const int rc = plan_roll(h, stride, n_actions, n_steps, action_fmt, per_step, &plan)) return rc;
+    if (plan.refused) return fallback ? kRollIneligible : fail(h, GSM_EINVAL, plan.refused);
+    auto no_memory = [&](hipError_t err, const char *what) {
+        return fallback ? kRollIneligible : hip_fail(h, err, what);
+    };
+    const gsm::RollShape &shape = plan.shape;
+    const gsm::GranLayout &lay = plan.lay;
+    const bool ragged = plan.p.path == gsm::kPathRagged;
+
+    // 3. what the handle's rollout slots share
+    hipError_t e = hipSuccess;
+    if (h->slab_bytes < plan.slab_bytes) {
+        void *fresh = nullptr;
+        e = hipMalloc(&fresh, plan.slab_bytes);
+        if (e != hipSuccess) return no_memory(e, "hipMalloc (rollout edge slabs)");
+        if (const int rc = replace_slabs(h, fresh, plan.slab_bytes)) return rc;
     }
-    if (!h->cap_stream) {
-        e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return hip_fail(h, e, "hipStreamCreate");
-    }
+    if (const int rc = ensure_status(h)) return rc;
+    if (const int rc = ensure_cap_stream(h)) return rc;
     // in the bound buffers, the edges of every step but the last go to a
     // scratch of the bound capacity (DevParams::RollOut); allocated once
     if (!per_step && !h->edge_scratch) {
         e = hipMalloc(&h->edge_scratch, 12 * (size_t)h->sz.edge_capacity);
         if (e != hipSuccess) {
             h->edge_scratch = nullptr;
-            if (fallback) return kRollIneligible;
-            return hip_fail(h, e, "hipMalloc (rollout edge scratch)");
+            return no_memory(e, "hipMalloc (rollout edge scratch)");
         }
     }
+
+    // 4. the slot: its granules, its timing events, the stored launch
     gsm_handle::Slot &sl = h->slots[slot];
     drop_slot(sl);
-    // a 16-byte header (unused), then 8-byte granules. Ragged and packed
-    // small envs: per-wave counts [K][xW] and group sums [K][xNG]; the tile
-    // path and the other segmented shapes (one env per workgroup or per
-    // wave): aggregates [K][nb], two halves of chunk sums [K][nc] kCsumStride
-    // apart (gsm_device.h roll_prefix) and two halves of pace counters
-    // (gsm_device.h pace_level). Zeroed once here — granules are tagged with the launch
-    // epoch, so replays never clear them; the untagged chunk sums and counters
-    // are zeroed by the launch before the one that uses them
-    // (ragged: then the placement words, gsm::PlaceArea)
-    const bool one_hop = !per_wave;   // one-hop prefix and pacing: the one-env-per-wave and tile rollouts
-    const size_t nc = ((size_t)nb + gsm::kPrefixChunk - 1) / gsm::kPrefixChunk;
-    if (one_hop && nc > (size_t)gsm::kWave) {   // roll_prefix: one chunk sum per lane
-        if (fallback) return kRollIneligible;
-        return fail(h, GSM_EINVAL, "GSM_GRAPH_ROLL: more than 4096 workgroups in one rollout launch");
-    }
-    const size_t csum_half = one_hop ? (size_t)K * nc * kCsumStride : 0;   // u64
-    const size_t pace_words = one_hop ? (size_t)gsm::kPaceKeys * gsm::kPaceStride : 0;   // u32, per half
-    const size_t gran_alloc = 16 + ((size_t)K * (per_wave ? (size_t)(xW + xNG) : (size_t)nb) +
-                                    2 * csum_half) * sizeof(uint64_t) +
-                              2 * pace_words * sizeof(uint32_t) +
-                              (ragged ? gsm::PlaceArea::words(xW) * sizeof(uint64_t) : 0);
-    e = gran_malloc(&sl.gran_base, &sl.gran, gran_alloc);
-    if (e != hipSuccess) {
-        sl.gran = nullptr;
-        if (fallback) return kRollIneligible;   // the per-step chain needs no granules
-        return hip_fail(h, e, "hipMalloc (rollout granules)");
-    }
+    e = gran_malloc(&sl.gran_base, &sl.gran, lay.bytes);
+    if (e != hipSuccess) return no_memory(e, "hipMalloc (rollout granules)");
     // Zeroed once (tag 0 never matches). Every launch then takes its own
     // epoch (next_launch_epoch, set in gsm_graph_launch): a memset or
     // store-zeroed allocation was seen to still show an agent-scope load
-    // granules left at that address by a freed graph's last replay, and with
-    // per-capture epochs those could carry this graph's tags.
-    e = gsm::launch_granule_init(sl.gran, gran_alloc, 0u, h->cap_stream);
+    // granules left at that address by a freed slot's last launch, and with
+    // per-capture epochs those could carry this slot's tags. The untagged
+    // chunk sums and counters are zeroed by the launch before the one that
+    // uses them.
+    e = gsm::launch_granule_init(sl.gran, lay.bytes, 0u, h->cap_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->cap_stream);
     if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "rollout granule init"); }
-    if (one_hop) {
-        uint64_t *const after = sl.gran + 2 + (size_t)K * nb;
-        sl.csum = after;
-        sl.csum_half = (int64_t)csum_half;
-        sl.pace = pace_on ? (uint32_t *)(after + 2 * csum_half) : nullptr;
-    }
-    const bool ends = (flags & GSM_GRAPH_TIME_ENDS) != 0;
-    sl.events.resize(ends ? 2 : 0, nullptr);
+    sl.lay = lay;
+    sl.paced = plan.knobs.pace_on && lay.pace[0].bytes != 0;
+    // timing (TIME_ENDS): the events bracket the rollout launch alone, so
+    // gsm_graph_kernel_ms reports its time per step
+    sl.events.resize((flags & GSM_GRAPH_TIME_ENDS) ? 2 : 0, nullptr);
     for (auto &ev : sl.events) {
         e = hipEventCreate(&ev);
         if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "hipEventCreate"); }
     }
-    e = hipGraphCreate(&sl.graph, 0);
-    if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "hipGraphCreate"); }
-    hipGraphNode_t prev = nullptr;
-    const char *what = "event node";
-    auto add_event = [&](hipEvent_t ev) -> hipError_t {
-        hipGraphNode_t n;
-        const hipError_t r = hipGraphAddEventRecordNode(&n, sl.graph, prev ? &prev : nullptr, prev ? 1 : 0, ev);
-        if (r == hipSuccess) prev = n;
-        return r;
-    };
-    if (e == hipSuccess && ends) { what = "event node"; e = add_event(sl.events[0]); }
     // all steps and their edges in one launch; the last step's sums go to the
     // bound edge-sum buffer (later eager emits read it)
-    if (!per_step) {
-        ro.eidx_mid = (int32_t *)h->edge_scratch;
-        ro.eattr_mid = (float *)(ro.eidx_mid + 2 * h->sz.edge_capacity);
-    }
+    gsm::DevParams &p = plan.p;
     p.actions = actions;
-    p.ro = ro;
+    if (!per_step) {
+        p.ro.eidx_mid = (int32_t *)h->edge_scratch;
+        p.ro.eattr_mid = (float *)(p.ro.eidx_mid + 2 * h->sz.edge_capacity);
+    }
+    gsm::DevParams::Roll r{};
+    r.actions = (const char *)actions;
+    r.stride = stride;
+    r.n_actions = n_actions;
+    r.K = n_steps;
+    r.xW = shape.xW;
+    r.xNG = shape.xNG;
+    r.depth = plan.depth;
+    r.slab_e = h->sz.max_edges_per_env;
     // ragged mixed: envs dealt to the SIMDs by cost when the grid fills every
     // SIMD with the same number of waves (GSM_ROLL_PLACE=0: env = wave index)
-    const int place_S = 4 * n_cu;
-    int place_R = 0;
-    if (ragged && h->place_order && xW % place_S == 0) place_R = xW / place_S;
-    // (GSM_ROLL_PLACE=2, a test knob: every wave registers, then the launch
-    // decides identity, the partial-residency fallback)
-    int place_force = 0;
-    if (const char *ev = getenv("GSM_ROLL_PLACE")) {
-        if (atoi(ev) == 0) place_R = 0;
-        if (atoi(ev) == 2) place_force = 1;
-    }
-    p.roll = gsm::DevParams::Roll{(const char *)actions, stride, n_actions, 0, K, xW, xNG, depth,
-                                  h->sz.max_edges_per_env, place_R, sl.gran + 2, h->roll_status, 0u, place_force,
-                                  (int32_t *)h->slab, place_R ? h->place_order : nullptr, place_S, pace_q};
-    p.roll.csum_stride = kCsumStride;   // (csum, pace: set per launch, gsm_graph_launch)
-    p.roll.gran_end = (uint64_t *)((char *)sl.gran + gran_alloc);
-    p.roll.slab_end = h->slab ? (int32_t *)((char *)h->slab + h->slab_bytes) : nullptr;
-    if (e == hipSuccess) {
-        what = "rollout kernel node";
-        hipKernelNodeParams kp = {};
-        void *args[] = {&p};
-        kp.func = const_cast<void *>(form.fn);
-        kp.gridDim = dim3(nb);
-        kp.blockDim = dim3(form.threads);
-        kp.sharedMemBytes = (unsigned)form.lds;
-        kp.kernelParams = args;
-        kp.extra = nullptr;
-        hipGraphNode_t n;
-        e = hipGraphAddKernelNode(&n, sl.graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp);
-        if (e == hipSuccess) prev = n;
-        sl.direct = true;
-        sl.fn = form.fn;
-        sl.grid = kp.gridDim;
-        sl.block = kp.blockDim;
-        sl.lds = kp.sharedMemBytes;
-        sl.args = p;
-    }
-    if (e == hipSuccess && ends) { what = "event node"; e = add_event(sl.events[1]); }
-    if (e != hipSuccess) {
-        drop_slot(sl);
-        char where[96];
-        snprintf(where, sizeof where, "rollout graph build (%s)", what);
-        return hip_fail(h, e, where);
-    }
-    e = hipGraphInstantiate(&sl.exec, sl.graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "hipGraphInstantiate"); }
-    e = hipGraphUpload(sl.exec, h->cap_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->cap_stream);
-    if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "hipGraphUpload"); }
-    // timing (TIME_ENDS): the events bracket the rollout launch alone, so
-    // gsm_graph_kernel_ms reports its time per step
+    r.place_S = 4 * plan.n_cu;
+    if (ragged && h->place_order && plan.knobs.place && shape.xW % r.place_S == 0) r.place_R = shape.xW / r.place_S;
+    r.place = r.place_R ? h->place_order : nullptr;
+    r.place_force = plan.knobs.place_force;
+    r.gran = gran_at<uint64_t>(sl.gran, lay.granules.off);
+    r.gran_end = gran_at<uint64_t>(sl.gran, lay.bytes);
+    r.status = h->roll_status;
+    r.slab = (int32_t *)h->slab;
+    r.slab_end = h->slab ? (int32_t *)((char *)h->slab + h->slab_bytes) : nullptr;
+    r.pace_q = plan.knobs.pace_q;
+    r.csum_stride = kCsumStride;   // (epoch, csum, pace: set per launch, gsm_graph_launch)
+    p.roll = r;
+    sl.fn = plan.form.fn;
+    sl.grid = dim3(shape.nb);
+    sl.block = dim3(plan.form.threads);
+    sl.lds = (unsigned)plan.form.lds;
+    sl.args = p;
     sl.each = false;
     sl.kern = GSM_GRAPH_STEP;
     sl.steps = n_steps;
@@ -1134,8 +1121,8 @@ int gsm_graph_info(gsm_handle *h, int32_t slot, int32_t *steps, int32_t *fused) 
     if (!h) return fail(nullptr, GSM_EINVAL, "handle is NULL");
     if (bad_slot(slot)) return fail(h, GSM_EINVAL, "bad graph slot");
     const gsm_handle::Slot &sl = h->slots[slot];
-    if (steps) *steps = sl.exec ? sl.steps : 0;
-    if (fused) *fused = sl.exec && sl.roll ? 1 : 0;
+    if (steps) *steps = sl.captured() ? sl.steps : 0;
+    if (fused) *fused = sl.roll ? 1 : 0;
     return GSM_OK;
 }
 
@@ -1198,10 +1185,7 @@ static int capture_impl(gsm_handle *h, int32_t slot, const void *actions, int64_
         e = hipMalloc(&h->bsum_alt, (size_t)h->sz.n_blocks * sizeof(int32_t) + 16);
         if (e != hipSuccess) { h->bsum_alt = nullptr; return hip_fail(h, e, "hipMalloc (edge-sum buffer)"); }
     }
-    if (!h->cap_stream) {
-        e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return hip_fail(h, e, "hipStreamCreate");
-    }
+    if (const int rc = ensure_cap_stream(h)) return rc;
     // The graph is built node by node (a linear chain) rather than by stream
     // capture: event-record nodes for timing are then explicit (the capture
     // path of the HIP runtime bundled with PyTorch rejects
@@ -1218,10 +1202,9 @@ static int capture_impl(gsm_handle *h, int32_t slot, const void *actions, int64_
     sl.kern = kern;
     e = hipGraphCreate(&sl.graph, 0);
     if (e != hipSuccess) { drop_slot(sl); return hip_fail(h, e, "hipGraphCreate"); }
-    if (lag && !h->roll_status) {   // the ragged lagged step's bounded wait reports through it
-        e = hipMalloc(&h->roll_status, 16);
-        if (e == hipSuccess) e = clear_status(h);
-        if (e != hipSuccess) { h->roll_status = nullptr; drop_slot(sl); return hip_fail(h, e, "hipMalloc (status)"); }
+    if (lag) {   // the ragged lagged step's bounded wait reports through the status word
+        const int rc = ensure_status(h);
+        if (rc) { drop_slot(sl); return rc; }
     }
     gsm::DevParams p = h->dp;
     p.mode = GSM_MODE_STEP;
@@ -1312,8 +1295,8 @@ int gsm_graph_launch(gsm_handle *h, int32_t slot, void *stream) {
     if (!h) return fail(nullptr, GSM_EINVAL, "handle is NULL");
     if (bad_slot(slot)) return fail(h, GSM_EINVAL, "bad graph slot");
     gsm_handle::Slot &sl = h->slots[slot];
-    if (!sl.exec) return fail(h, GSM_ESTATE, "no graph captured in this slot");
-    if (sl.direct) {   // a rollout graph: its one kernel, launched directly
+    if (!sl.captured()) return fail(h, GSM_ESTATE, "no graph captured in this slot");
+    if (sl.roll) {   // a rollout slot: its stored kernel launch
         // (GSM_GRAPH_TIME_ENDS: events recorded on the stream around it — as
         // graph event nodes they added ≈7% to the launch they bracketed)
         hipStream_t st = as_stream(stream);
@@ -1341,14 +1324,13 @@ int gsm_graph_launch(gsm_handle *h, int32_t slot, void *stream) {
         }
         sl.args.roll.epoch = fresh_epoch(sl.last_epoch);   // copied with the arguments at the launch
         const int par = (int)(sl.launches & 1u);
-        if (sl.csum) {
-            sl.args.roll.csum = sl.csum + par * sl.csum_half;
-            sl.args.roll.csum_next = sl.csum + (1 - par) * sl.csum_half;
+        if (sl.lay.csum[0].bytes) {
+            sl.args.roll.csum = gran_at<uint64_t>(sl.gran, sl.lay.csum[par].off);
+            sl.args.roll.csum_next = gran_at<uint64_t>(sl.gran, sl.lay.csum[1 - par].off);
         }
-        if (sl.pace) {
-            const size_t half = (size_t)gsm::kPaceKeys * gsm::kPaceStride;
-            sl.args.roll.pace = sl.pace + par * half;
-            sl.args.roll.pace_next = sl.pace + (1 - par) * half;
+        if (sl.paced) {
+            sl.args.roll.pace = gran_at<uint32_t>(sl.gran, sl.lay.pace[par].off);
+            sl.args.roll.pace_next = gran_at<uint32_t>(sl.gran, sl.lay.pace[1 - par].off);
         }
         void *args[] = {&sl.args};
         e = sl.events.empty() ? hipSuccess : hipEventRecord(sl.events.front(), st);
@@ -1371,7 +1353,7 @@ int gsm_graph_kernel_ms(gsm_handle *h, int32_t slot, float *step_ms, float *emit
     if (!h) return fail(nullptr, GSM_EINVAL, "handle is NULL");
     if (bad_slot(slot)) return fail(h, GSM_EINVAL, "bad graph slot");
     const gsm_handle::Slot &sl = h->slots[slot];
-    if (!sl.exec || sl.events.empty()) return fail(h, GSM_ESTATE, "no timed graph in this slot");
+    if (!sl.captured() || sl.events.empty()) return fail(h, GSM_ESTATE, "no timed graph in this slot");
     float total = 0;
     hipError_t e = hipEventElapsedTime(&total, sl.events.front(), sl.events.back());
     if (e != hipSuccess) return hip_fail(h, e, "hipEventElapsedTime");

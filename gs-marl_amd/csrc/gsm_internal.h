@@ -1,6 +1,7 @@
 // Internal (non-ABI) declarations shared by gsm_kernels.hip and gsm_abi.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace gsm {
@@ -171,6 +172,11 @@ struct DevParams {
         int64_t as_s;
     } ro;
 };
+// the kernarg as the kernels were compiled to read it: a host-side change
+// that moves a field fails here, not in a launch
+static_assert(sizeof(DevParams) == 776 && offsetof(DevParams, roll) == 456 && offsetof(DevParams, ro) == 616,
+              "DevParams layout");
+static_assert(sizeof(DevParams::Roll) == 160 && sizeof(DevParams::RollOut) == 160, "Roll / RollOut layout");
 
 // where an emission writes its edges
 struct EdgeSink {

@@ -305,9 +305,11 @@ int gsm_graph_capture(gsm_handle *h, int32_t slot, const void *actions, int64_t 
 int gsm_graph_capture_into(gsm_handle *h, int32_t slot, const void *actions, int64_t action_stride_bytes,
                            int32_t n_actions, int32_t n_steps, int action_fmt, const gsm_outputs *per_step);
 /* Launch the graph in `slot` on `stream` (stream-ordered, asynchronous). A
- * rollout slot (GSM_GRAPH_ROLL, or a rollout buffer's single launch) is its one
- * kernel launched directly, with a fresh launch epoch for its hand-off tags and
- * its half of the slot's pacing counters; so it cannot be recorded into a
+ * rollout slot (GSM_GRAPH_ROLL, or a rollout buffer's single launch) holds a
+ * kernel launch, not a hipGraph: the stored kernel is dispatched with a fresh
+ * launch epoch for its hand-off tags and its half of the slot's chunk sums and
+ * pacing counters (the environment knobs of the rollouts: INTEGRATION.md,
+ * "Environment knobs"); so it cannot be recorded into a
  * stream capture (GSM_ESTATE on a capturing stream: capture the per-step chain
  * instead). The rollout slots of a handle share its state and scratch, so their
  * launches never overlap: a launch on a different stream than the handle's
