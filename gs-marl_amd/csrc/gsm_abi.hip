@@ -1816,6 +1816,46 @@ int gsm_critic_eval_bwd(const float *g, const float *x, int64_t x_row_stride, co
     return GSM_OK;
 }
 
+int gsm_ppo_loss_work_floats(int64_t n_rows, int64_t *n_floats) {
+    if (n_rows < 0 || n_rows >= ((int64_t)1 << 31)) return fail(nullptr, GSM_EINVAL, "n_rows must be in [0, 2^31)");
+    if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
+    *n_floats = gsm::ppo_loss_work_floats();
+    return GSM_OK;
+}
+
+int gsm_ppo_loss(const float *logp, const float *ent, const float *values, const float *logp_old, const float *adv,
+                 const float *v_old, const float *ret, const float *weight, const int32_t *n_valid, int64_t n_envs,
+                 int32_t n_agents, int32_t n_out, const float *multiplier, float clip, float value_clip,
+                 float ent_coef, float value_coef, float *work, float *loss, float *stats, float *g_logp,
+                 float *g_ent, float *g_values, int32_t *status, void *stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    // the shape limits, before anything else is looked at
+    if (n_out < 1 || n_out > 2) return fail(nullptr, GSM_EINVAL, "n_out must be 1 or 2");
+    if (n_agents < 1 || n_envs < 0 || n_envs >= lim || n_envs * n_agents >= lim)
+        return fail(nullptr, GSM_EINVAL, "n_agents >= 1, n_envs >= 0 and n_envs*n_agents < 2^31");
+    if (n_out == 2 && !multiplier) return fail(nullptr, GSM_EINVAL, "multiplier is NULL with n_out == 2");
+    if (!work || !loss || !stats) return fail(nullptr, GSM_EINVAL, "work, loss or stats is NULL");
+    const int n_g = (g_logp != nullptr) + (g_ent != nullptr) + (g_values != nullptr);
+    if (n_g != 0 && n_g != 3) return fail(nullptr, GSM_EINVAL, "g_logp, g_ent and g_values: all or none");
+    if (n_envs > 0 && (!logp || !ent || !values || !logp_old || !adv || !v_old || !ret))
+        return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
+    gsm::LossParams p = {};
+    p.logp = logp, p.ent = ent, p.values = values, p.logp_old = logp_old;
+    p.adv = adv, p.v_old = v_old, p.ret = ret, p.weight = weight;
+    p.n_valid = n_valid;
+    p.lam = multiplier;
+    p.R = n_envs * n_agents;
+    p.n_agents = n_agents, p.nO = n_out;
+    p.ratio_lo = (float)(1.0 - (double)clip), p.ratio_hi = (float)(1.0 + (double)clip);
+    p.value_clip = value_clip, p.ent_coef = ent_coef, p.value_coef = value_coef;
+    p.work = work, p.loss = loss, p.stats = stats;
+    p.g_logp = g_logp, p.g_ent = g_ent, p.g_values = g_values;
+    p.status = status;
+    const hipError_t e = gsm::launch_ppo_loss(p, as_stream(stream));
+    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_ppo_loss launch");
+    return GSM_OK;
+}
+
 int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
             int32_t n_agents, float gamma, float gamma_lambda, float *ret, void *stream) {
     const int64_t lim = (int64_t)1 << 31;

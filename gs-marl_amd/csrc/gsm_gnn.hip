@@ -1582,3 +1582,5 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
 #include "gsm_actor.h"
 // the critic head: gsm_critic_eval / gsm_critic_eval_bwd
 #include "gsm_critic.h"
+// the PPO / Lagrangian loss: gsm_ppo_loss
+#include "gsm_loss.h"

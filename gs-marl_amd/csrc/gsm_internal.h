@@ -357,6 +357,22 @@ hipError_t launch_critic_forward(const CriticParams &p, int hidden, hipStream_t 
 int64_t critic_backward_work_floats(int in, int hidden, int nO);
 hipError_t launch_critic_backward(const CriticParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
                                   hipStream_t s);
+// the PPO / Lagrangian loss (gsm_loss.h): what its launcher takes. R = n_envs *
+// n_agents rows; values, adv, v_old, ret and g_values head-major [nO][R]; lam
+// the device multiplier; ratio_lo / ratio_hi = 1 -/+ clip rounded once
+struct LossParams {
+    const float *logp, *ent, *values, *logp_old, *adv, *v_old, *ret, *weight;
+    const int32_t *n_valid;
+    const float *lam;
+    int64_t R;
+    int n_agents, nO;
+    float ratio_lo, ratio_hi, value_clip, ent_coef, value_coef;
+    float *work, *loss, *stats, *g_logp, *g_ent, *g_values;
+    int32_t *status;
+};
+// floats of workspace launch_ppo_loss needs: one [8] partial per workgroup of its capped grid
+int64_t ppo_loss_work_floats();
+hipError_t launch_ppo_loss(const LossParams &p, hipStream_t s);
 hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
                       float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,

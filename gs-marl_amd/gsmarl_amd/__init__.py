@@ -9,11 +9,13 @@ from .rollout import GraphRolloutBuffer
 from . import gnn
 from . import policy
 from .policy import ActorHead, CriticHead, PopArt
+from . import loss
+from .loss import LagrangeMultiplier, PPOLagrangianLoss
 from . import render
 from . import distributed
 
 __version__ = "0.1.0"
 __all__ = ["EnvConfig", "GpuBatchEnv", "MultiAgentEnv", "MultiAgentConstrainEnv",
            "MultiAgentGraphConstrainEnv", "make_env", "GpuGraphVecEnv", "make_train_env", "make_eval_env",
-           "GraphRolloutBuffer", "gnn", "policy", "ActorHead", "CriticHead", "PopArt", "render",
-           "distributed"]
+           "GraphRolloutBuffer", "gnn", "policy", "ActorHead", "CriticHead", "PopArt", "loss",
+           "PPOLagrangianLoss", "LagrangeMultiplier", "render", "distributed"]

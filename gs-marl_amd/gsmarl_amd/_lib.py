@@ -25,6 +25,7 @@ CONV_SKIP, CONV_MAX_ENTITIES = 1, 288
 ACTOR_DETERMINISTIC = 1
 ACTOR_NONFINITE, ACTOR_BAD_ACTION = 1, 2
 CRITIC_NONFINITE, CRITIC_BAD_COUNT = 1, 2
+LOSS_NONFINITE, LOSS_BAD_COUNT, LOSS_BAD_WEIGHT = 1, 2, 4
 
 
 class GsmConfig(C.Structure):
@@ -132,6 +133,9 @@ SIGNATURES = {
     "gsm_critic_backward_work_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "gsm_critic_eval_bwd": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gsm_ppo_loss_work_floats": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "gsm_ppo_loss": (C.c_int, [_P] * 9 + [C.c_int64, C.c_int32, C.c_int32, _P, C.c_float, C.c_float, C.c_float,
+                               C.c_float] + [_P] * 8),
     "gsm_gae": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "gsm_render": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

@@ -676,6 +676,64 @@ int gsm_critic_eval_bwd(const float *g, const float *x, int64_t x_row_stride, co
                         int32_t n_agents, int32_t in_features, int32_t hidden, int32_t n_out, float *work,
                         float *dw1, float *db1, float *dw2, float *db2, float *dx, int32_t *status, void *stream);
 
+/* The clipped PPO / Lagrangian loss the two heads end in: the loss, eight
+ * statistics and the gradients with respect to logp, entropy and the values,
+ * in one launch pair. Rows r = b*n_agents + i, R = n_envs*n_agents; logp, ent,
+ * logp_old f32 [R]; values, adv, v_old, ret f32 [n_out][R], head-major as
+ * gsm_critic_eval writes them (head 0 the reward critic, head 1 the cost
+ * critic). weight f32 [R] or NULL (1); n_valid int32 [n_envs] or NULL, clamped
+ * to [0, n_agents]. multiplier: device f32 [1], the Lagrange multiplier, read
+ * when the kernel runs (a captured graph sees an updated multiplier); NULL
+ * only with n_out == 1. With lam = multiplier[0]:
+ *   w_r   = weight[r] * [i < n_valid[b]];  W = sum_r w_r
+ *   A     = adv[0][r] - lam * adv[1][r]            (n_out == 1: adv[0][r])
+ *   ratio = expf(logp - logp_old)                  (the actor head's expf)
+ *   pol   = -min(ratio * A, clamp(ratio, 1 - clip, 1 + clip) * A)
+ *   vclip = v_old + clamp(v - v_old, -value_clip, value_clip)
+ *   val_o = max((v_o - ret_o)^2, (vclip_o - ret_o)^2)
+ *   t_r   = (pol - ent_coef * ent) + value_coef * (val_0 + val_1)
+ *   loss  = (sum_r w_r * t_r) / W
+ * every line one correctly rounded fp32 operation at a time; 1 -/+ clip are
+ * formed in double and rounded once. A row with w_r == 0 is not used in any
+ * input (it may hold NaN; a row past n_valid[b] may hold NaN in weight too)
+ * and gets the gradient 0.0. The gradients, d(loss) / d(input), [R], [R] and
+ * [n_out][R], each written as (w_r * d_r) * (1.0f / W):
+ *   g_logp:   d = -(ratio * A)  if 1 - clip <= ratio <= 1 + clip or
+ *                               ratio * A < clamp(ratio, ..) * A;  else 0
+ *   g_ent:    d = -ent_coef
+ *   g_values: d = (2 * (v - ret)) * value_coef  if |v - v_old| <= value_clip
+ *                               or (v - ret)^2 > (vclip - ret)^2;  else 0
+ * g_logp, g_ent and g_values all NULL: not wanted (the second launch is then
+ * one workgroup). loss f32 [1]. stats f32 [8]: the weighted means (sum_r w_r
+ * x_r) / W of [0] t (the loss), [1] pol, [2] ent, [3] val_0, [4] val_1 (0 for
+ * an absent head), [5] logp_old - logp (the approximate KL), [6] [ratio
+ * outside [1 - clip, 1 + clip]] (the clip fraction), and [7] W. With R == 0 or
+ * W == 0 loss, stats and the gradients are zeros; nothing divides by zero.
+ * work: device f32, gsm_ppo_loss_work_floats of them (one [8] partial per
+ * workgroup of a capped grid). The first launch adds a thread's rows, the 64
+ * lanes of a wave and the waves of a workgroup in a fixed order; the second
+ * adds the partials in one fixed order, the same in every workgroup. No float
+ * atomics: the summation order depends on the shape alone (not on alignment:
+ * 16-byte loads are used when R % 4 == 0 and every pointer is 16-byte
+ * aligned, scalar loads of the same rows in the same order otherwise), so two
+ * calls on the same inputs give the same bits in every output.
+ * status (device int32 [1], OR-ed, zeroed by the caller; NULL: not wanted):
+ * GSM_LOSS_NONFINITE: a row with w_r != 0 gave a non-finite t (it is added, as
+ * autograd would); GSM_LOSS_BAD_COUNT: an n_valid[b] outside [0, n_agents],
+ * clamped; GSM_LOSS_BAD_WEIGHT: a weight negative or non-finite, taken as 0.
+ * Shape limits (GSM_EINVAL, checked first, nothing is launched): n_out 1 or 2;
+ * n_agents >= 1; n_envs*n_agents < 2^31; multiplier NULL with n_out == 2.
+ * Stateless; asynchronous on `stream`; no host reads, so it can be captured. */
+#define GSM_LOSS_NONFINITE 1  /* status: a weighted row had a non-finite term      */
+#define GSM_LOSS_BAD_COUNT 2  /* status: an n_valid[b] outside [0, n_agents]       */
+#define GSM_LOSS_BAD_WEIGHT 4 /* status: a weight negative or non-finite           */
+int gsm_ppo_loss_work_floats(int64_t n_rows, int64_t *n_floats);
+int gsm_ppo_loss(const float *logp, const float *ent, const float *values, const float *logp_old, const float *adv,
+                 const float *v_old, const float *ret, const float *weight, const int32_t *n_valid, int64_t n_envs,
+                 int32_t n_agents, int32_t n_out, const float *multiplier, float clip, float value_clip,
+                 float ent_coef, float value_coef, float *work, float *loss, float *stats, float *g_logp,
+                 float *g_ent, float *g_values, int32_t *status, void *stream);
+
 /* GAE returns of a stored episode of T = n_steps actions in one launch, with
  * BN = [n_envs][n_agents]: reward f32 [T]BN (entry t: the reward of action t),
  * value f32 [T+1]BN, done uint8 [T+1][n_envs] (slot t+1: action t ended the
