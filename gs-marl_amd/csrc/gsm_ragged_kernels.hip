@@ -303,6 +303,30 @@ struct LsaWarm {
 //    start cannot use):
 //  * cold: scipy's rectangular_lsap recurrence from scratch (oracle/lsa_ref.py),
 //    rows in order, with its tie rules.
+//
+// The bound on the duals (kLsaDualMax). The cache is the caller's memory and
+// need not belong to the state (a restored checkpoint, an unwritten buffer, an
+// auto-reset), and the argument above holds for the reduced costs the
+// certificate COMPUTES only as far as they are the exact ones. It forms
+// r~ = fl(fl(C - u_i) - v_j): with a = fl(C - u_i), |a| <= |v_j| + |a - v_j|,
+// so |r~ - r| <= 2^-53 |v_j| + 2^-52 |r~| against the exact r = C - u_i - v_j
+// of the SAME float64 duals (any u, v are duals of some sort; only this
+// evaluation has to be exact, not the arithmetic that produced them). Duals
+// of 1e16 quantise every r~ to a multiple of 2, and the certificate then
+// proves unique the optimum of that quantised problem: a cache v = [1e16, 0]
+// made a 2 x 2 env return the costlier assignment, certified. So the
+// certificate also requires |v_j| <= V = 2^12 on every column. Then each test
+// it makes errs by at most e = 2^-53 V = 2^-41 = 4.6e-13 (the 2^-52 |r~| term
+// is relative and moves no threshold by more than 1e-24): exact r >= -1e-11
+// - e everywhere, <= 1e-11 + e on the matching, > 1e-9 - e on a pair of every
+// other assignment, which therefore costs at least
+//   (1e-9 - e) - (N - 1)(1e-11 + e) - N (1e-11 + e) >= 1e-9 - 2N (1e-11 + e)
+// more: 3.3e-10 at N = 32, of which the bound spends 2N e = 2.9e-11. A
+// cache with a dual beyond V is not tried at all (one comparison on the value
+// just loaded, which also rejects inf and NaN: such a cache is not the last
+// step's), and the cold path writes back duals of the size of the costs, so a
+// bad cache lasts one step. Duals of real trajectories stay below 4
+// (profiles/lsa_warm_cases.json), a factor 1000 under V.
 #ifdef GSM_STAMPS   // diagnostic builds: s_memtime at the assignment's phase boundaries
 #define LSA_T(k)                                                                   \
     do {                                                                           \
@@ -338,6 +362,7 @@ __device__ __forceinline__ LsaLds lsa_lds(unsigned char *lds, int nmax) {
 #ifndef GSM_LSA_ROLL_CHUNK
 #define GSM_LSA_ROLL_CHUNK 4
 #endif
+constexpr double kLsaDualMax = 4096.0;   // V above; oracle/lsa_ref.py DUAL_MAX
 template <bool kColLds = false>
 __device__ int wave_lsa(int N, int lane, float2 pa, float2 slot, const float2 *s_agent, const LsaLds &sl, float *own,
                         LsaWarm w, int *iters = nullptr, uint64_t *tm = nullptr) {
@@ -521,6 +546,7 @@ __device__ int wave_lsa(int N, int lane, float2 pa, float2 slot, const float2 *s
         // by VGPR arithmetic only (no per-column compare or select): the
         // smallest reduced cost over all columns (>= -1e-11 together with
         // |r| <= 1e-11 on the matched column is the same test as per column),
+        // the lane's own column dual within kLsaDualMax,
         // and the tight bits r <= tau as the sign of r - succ(tau), shifted in
         // (columns past N hold +inf: never tight)
         if (lane < kRaggedMaxAgents) sl.v[lane] = col ? v : 0.0;
@@ -549,7 +575,7 @@ __device__ int wave_lsa(int N, int lane, float2 pa, float2 slot, const float2 *s
                 }
             }
             const double rc = ci >= 0 ? (double)crow[ci] - u - sl.v[ci] : 0.0;
-            good = rmin >= -1e-11 && fabs(rc) <= 1e-11;
+            good = rmin >= -1e-11 && fabs(rc) <= 1e-11 && fabs(v) <= kLsaDualMax;   // lane = row and column
             if (ci >= 0) tight &= ~(1u << ci);
         }
         if (!__all(good)) {
@@ -576,7 +602,7 @@ __device__ int wave_lsa(int N, int lane, float2 pa, float2 slot, const float2 *s
     if (w.v) {
         const double v0 = col ? w.v[lane] : 0.0;    // column duals: lane = column
         const int c0 = col ? w.col[lane] : -1;      // previous matching: lane = row
-        if (__all(!col || __builtin_isfinite(v0))) {
+        if (__all(!col || fabs(v0) <= kLsaDualMax)) {   // finite and within the bound (false for NaN)
             // feasible row duals from the previous v; rows whose previous
             // column still attains their minimum keep it, the others are
             // re-matched by scipy's augmenting step. (Keeping the whole

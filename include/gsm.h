@@ -157,8 +157,15 @@ typedef struct gsm_buffers {
      * of each env's last assignment, kept by the library between launches.
      * A warm-started assignment is used only when certified to be the unique
      * optimum — then it IS scipy's result; otherwise the scipy recurrence runs
-     * from scratch. Initialise lsa_col to -1 (lsa_v to 0). */
-    double *lsa_v;            /* [B][N] */
+     * from scratch. Initialise lsa_col to -1 (lsa_v to 0).
+     * The buffers need not belong to the state (set_state does not carry
+     * them, and they survive resets): any contents are safe. lsa_col entries
+     * outside [0, N_env) count as "no column"; a cache with a dual that is
+     * non-finite or exceeds 4096 in magnitude is not used, and no assignment
+     * is certified with such a dual (at larger duals float64 rounding of the
+     * reduced costs reaches the certificate's 1e-9 margin). Such an env is
+     * solved from scratch, which rewrites its cache. */
+    double *lsa_v;            /* [B][N], |v| <= 4096 to be used */
     int32_t *lsa_col;         /* [B][N] */
     int32_t *lsa_stats;       /* [B][2] optional counters: certified warm starts, assignments solved */
 } gsm_buffers;
