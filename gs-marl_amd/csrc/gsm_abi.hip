@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -110,6 +111,36 @@ int hip_fail(gsm_handle *h, hipError_t e, const char *where) {
     char buf[256];
     snprintf(buf, sizeof buf, "%s: hipError %d (%s)", where, (int)e, hipGetErrorString(e));
     return fail(h, GSM_EHIP, buf);
+}
+
+// the tail of an entry point that launched: `what` names the step in the error
+int launched(hipError_t e, const char *what) { return e == hipSuccess ? GSM_OK : hip_fail(nullptr, e, what); }
+
+// argument checks that several entry points share, each with its one message
+int heads_shape(int32_t heads, int32_t channels) {
+    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
+        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    return GSM_OK;
+}
+int nodes_range(int64_t n_nodes) {
+    return n_nodes < 0 || n_nodes >= ((int64_t)1 << 40) ? fail(nullptr, GSM_EINVAL, "bad n_nodes") : GSM_OK;
+}
+int edges_range(int64_t n_edges) {
+    return n_edges < 0 || n_edges >= ((int64_t)1 << 31) ? fail(nullptr, GSM_EINVAL, "bad n_edges") : GSM_OK;
+}
+
+// zero bytes at each (pointer, bytes) in order until the first error; a nullptr is skipped
+struct Zeroed {
+    void *ptr;
+    size_t bytes;
+};
+hipError_t zero_all(std::initializer_list<Zeroed> list, hipStream_t s) {
+    for (const Zeroed &z : list) {
+        if (!z.ptr) continue;
+        const hipError_t e = hipMemsetAsync(z.ptr, 0, z.bytes, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 int align16(int x) { return (x + 15) & ~15; }
@@ -1386,9 +1417,8 @@ static int attn_forward(const float *q, const float *k, const float *v, const fl
                         const int64_t *row_ptr, const int32_t *col, const float *skip, int64_t n_nodes,
                         int32_t heads, int32_t channels, float scale, float *out, float *lse, bool want_lse,
                         void *stream, const char *what) {
-    if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 40)) return fail(nullptr, GSM_EINVAL, "bad n_nodes");
-    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
-        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (const int rc = nodes_range(n_nodes)) return rc;
+    if (const int rc = heads_shape(heads, channels)) return rc;
     if (n_nodes == 0) return GSM_OK;
     if (!q || !k || !v || !row_ptr || !col || !out || (want_lse && !lse))
         return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
@@ -1396,8 +1426,7 @@ static int attn_forward(const float *q, const float *k, const float *v, const fl
     const hipError_t e = gsm::launch_attn_aggregate(q, k, v, edge_w, w_e, row_ptr, col, skip, n_nodes,
                                                     heads * channels, channels, scale, out, lse,
                                                     as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, what);
-    return GSM_OK;
+    return launched(e, what);
 }
 
 int gsm_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w, const float *w_e,
@@ -1417,10 +1446,9 @@ int gsm_attn_aggregate_fwd(const float *q, const float *k, const float *v, const
 
 int gsm_attn_backward_work_floats(int64_t n_nodes, int64_t n_edges, int32_t heads, int32_t channels,
                                   int64_t *n_floats) {
-    if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 40)) return fail(nullptr, GSM_EINVAL, "bad n_nodes");
-    if (n_edges < 0 || n_edges >= ((int64_t)1 << 31)) return fail(nullptr, GSM_EINVAL, "bad n_edges");
-    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
-        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (const int rc = nodes_range(n_nodes)) return rc;
+    if (const int rc = edges_range(n_edges)) return rc;
+    if (const int rc = heads_shape(heads, channels)) return rc;
     if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
     *n_floats = gsm::attn_backward_work_floats(n_edges, heads, heads * channels);
     return GSM_OK;
@@ -1432,34 +1460,29 @@ int gsm_attn_aggregate_bwd(const float *grad_out, const float *q, const float *k
                            const int32_t *t_edge, const int32_t *t_tgt, int64_t n_nodes, int64_t n_edges,
                            int32_t heads, int32_t channels, float scale, float *work, float *dq, float *dk,
                            float *dv, float *dedge_w, float *dw_e, void *stream) {
-    if (n_nodes < 0 || n_nodes >= ((int64_t)1 << 40)) return fail(nullptr, GSM_EINVAL, "bad n_nodes");
-    if (n_edges < 0 || n_edges >= ((int64_t)1 << 31)) return fail(nullptr, GSM_EINVAL, "bad n_edges");
-    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
-        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (const int rc = nodes_range(n_nodes)) return rc;
+    if (const int rc = edges_range(n_edges)) return rc;
+    if (const int rc = heads_shape(heads, channels)) return rc;
     if (n_nodes == 0 && n_edges > 0) return fail(nullptr, GSM_EINVAL, "edges without nodes");
     if (!!edge_w != !!w_e) return fail(nullptr, GSM_EINVAL, "edge_w and w_e go together");
     if (dedge_w && !edge_w) return fail(nullptr, GSM_EINVAL, "dedge_w needs edge_w");
     hipStream_t s = as_stream(stream);
     const size_t row = sizeof(float) * (size_t)(heads * channels);
-    hipError_t e = hipSuccess;
     if (n_nodes == 0 || n_edges == 0) {
         // no edges: every gradient but dskip (= grad_out, the caller's) is 0
         if (n_nodes > 0 && (!dq || !dk || !dv)) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
-        if (n_nodes > 0) e = hipMemsetAsync(dq, 0, row * (size_t)n_nodes, s);
-        if (n_nodes > 0 && e == hipSuccess) e = hipMemsetAsync(dk, 0, row * (size_t)n_nodes, s);
-        if (n_nodes > 0 && e == hipSuccess) e = hipMemsetAsync(dv, 0, row * (size_t)n_nodes, s);
-        if (dw_e && e == hipSuccess) e = hipMemsetAsync(dw_e, 0, row, s);
-        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_attn_aggregate_bwd memset");
-        return GSM_OK;
+        const size_t all = row * (size_t)n_nodes;   // n_nodes == 0: dq, dk, dv are not looked at
+        return launched(zero_all({{n_nodes ? dq : nullptr, all}, {n_nodes ? dk : nullptr, all},
+                                  {n_nodes ? dv : nullptr, all}, {dw_e, row}}, s),
+                        "gsm_attn_aggregate_bwd memset");
     }
     if (!grad_out || !q || !k || !v || !row_ptr || !col || !out || !lse || !t_ptr || !t_edge || !t_tgt || !work ||
         !dq || !dk || !dv)
         return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
-    e = gsm::launch_attn_backward(grad_out, q, k, v, edge_w, w_e, row_ptr, col, out, skip, lse, t_ptr, t_edge,
+    const hipError_t e = gsm::launch_attn_backward(grad_out, q, k, v, edge_w, w_e, row_ptr, col, out, skip, lse, t_ptr, t_edge,
                                   t_tgt, n_nodes, n_edges, heads * channels, channels, scale, work, dq, dk, dv,
                                   dedge_w, dw_e, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_attn_aggregate_bwd launch");
-    return GSM_OK;
+    return launched(e, "gsm_attn_aggregate_bwd launch");
 }
 
 static int graph_batch_shape(int64_t n_slots, int64_t n_envs, int64_t edge_capacity, int64_t n_samples) {
@@ -1481,8 +1504,7 @@ int gsm_graph_batch_ptr(const int64_t *edge_ptr, int64_t n_slots, int64_t n_envs
         return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
     const hipError_t e = gsm::launch_graph_batch_ptr(edge_ptr, n_slots, n_envs, edge_capacity, t_idx, b_idx,
                                                      n_samples, sample_ptr, status, as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_graph_batch_ptr launch");
-    return GSM_OK;
+    return launched(e, "gsm_graph_batch_ptr launch");
 }
 
 int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, const float *edge_attr,
@@ -1505,23 +1527,20 @@ int gsm_graph_batch_gather(const float *node_feat, const int32_t *edge_index, co
     hipStream_t s = as_stream(stream);
     if (n_samples == 0) {
         const hipError_t e = hipMemsetAsync(row_ptr, 0, sizeof(int64_t), s);
-        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_graph_batch_gather memset");
-        return GSM_OK;
+        return launched(e, "gsm_graph_batch_gather memset");
     }
     const hipError_t e = gsm::launch_graph_batch_gather(node_feat, edge_index, edge_attr, edge_ptr, n_slots, n_envs,
                                                         n_entities, edge_capacity, t_idx, b_idx, sample_ptr,
                                                         n_samples, n_edges, node_feat_out, row_ptr, col,
                                                         edge_attr_out, t_edge, status, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_graph_batch_gather launch");
-    return GSM_OK;
+    return launched(e, "gsm_graph_batch_gather launch");
 }
 
 // the shape limits the fused first layer's forward and backward share
 static int env_conv_shape(int64_t n_envs, int32_t n_entities, int64_t edge_limit, int64_t edge_row_stride,
                           int32_t heads, int32_t channels, int32_t flags, int32_t n_rows_out) {
     const int64_t lim = (int64_t)1 << 31;
-    if (heads < 1 || channels < 1 || (channels & (channels - 1)) || heads * channels > 64)
-        return fail(nullptr, GSM_EINVAL, "need channels a power of two and heads*channels <= 64");
+    if (const int rc = heads_shape(heads, channels)) return rc;
     if (n_entities < 1 || n_entities > GSM_CONV_MAX_ENTITIES)
         return fail(nullptr, GSM_EINVAL, "n_entities must be in [1, 288]");
     if (n_envs < 0 || n_envs >= lim || n_envs * n_entities >= lim)
@@ -1560,8 +1579,7 @@ static int env_conv_forward(const float *node_feat, const int64_t *edge_ptr, con
                                               w, w_e, n_envs, n_entities, heads * channels, channels, scale,
                                               (flags & GSM_CONV_SKIP) != 0, n_rows_out, out, lse, row_ptr_out,
                                               status, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, what);
-    return GSM_OK;
+    return launched(e, what);
 }
 
 int gsm_env_conv(const float *node_feat, const int64_t *edge_ptr, const int32_t *edge_index,
@@ -1606,10 +1624,7 @@ int gsm_env_conv_bwd(const float *grad_out, const float *node_feat, const int64_
     const bool skip = (flags & GSM_CONV_SKIP) != 0;
     const size_t row = sizeof(float) * (size_t)(heads * channels);
     if (n_envs == 0) {
-        hipError_t e = hipMemsetAsync(dw, 0, row * 8 * (skip ? 4 : 3), s);
-        if (dw_e && e == hipSuccess) e = hipMemsetAsync(dw_e, 0, row, s);
-        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv_bwd memset");
-        return GSM_OK;
+        return launched(zero_all({{dw, row * 8 * (skip ? 4 : 3)}, {dw_e, row}}, s), "gsm_env_conv_bwd memset");
     }
     if (!grad_out || !node_feat || !edge_ptr || !w || !out || !lse || !work)
         return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
@@ -1620,8 +1635,7 @@ int gsm_env_conv_bwd(const float *grad_out, const float *node_feat, const int64_
                                                        edge_attr, edge_limit, w, w_e, out, lse, n_envs, n_entities,
                                                        heads * channels, channels, scale, skip, n_rows_out, work,
                                                        dw, dw_e, status, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_env_conv_bwd launch");
-    return GSM_OK;
+    return launched(e, "gsm_env_conv_bwd launch");
 }
 
 // the shape limits of the actor head, before anything else is looked at
@@ -1640,7 +1654,7 @@ static int actor_shape(int64_t x_row_stride, int64_t n_envs, int32_t n_agents, i
     return GSM_OK;
 }
 
-static int actor_pointers(const float *x, const float *w1, const float *b1, const float *w2, const float *b2,
+static int head_pointers(const float *x, const float *w1, const float *b1, const float *w2, const float *b2,
                           int32_t hidden) {
     if (!x || !w2 || !b2 || (hidden && (!w1 || !b1))) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
     if ((uintptr_t)x % 16) return fail(nullptr, GSM_EINVAL, "x must be 16-byte aligned");
@@ -1670,7 +1684,7 @@ int gsm_actor_sample(const float *x, int64_t x_row_stride, const float *w1, cons
     if (const int rc = actor_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_actions)) return rc;
     if (flags & ~GSM_ACTOR_DETERMINISTIC) return fail(nullptr, GSM_EINVAL, "unknown flags");
     if (n_envs == 0) return GSM_OK;
-    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (const int rc = head_pointers(x, w1, b1, w2, b2, hidden)) return rc;
     if (!actions || !logp) return fail(nullptr, GSM_EINVAL, "actions or logp is NULL");
     gsm::ActorParams p = actor_params(x, x_row_stride, w1, b1, w2, b2, n_envs, n_agents, in_features, n_actions,
                                       status);
@@ -1679,8 +1693,7 @@ int gsm_actor_sample(const float *x, int64_t x_row_stride, const float *w1, cons
     p.deterministic = (flags & GSM_ACTOR_DETERMINISTIC) != 0;
     p.actions_out = actions, p.logp = logp, p.entropy = entropy, p.logits_out = logits_out;
     const hipError_t e = gsm::launch_actor_forward(p, hidden, false, as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_sample launch");
-    return GSM_OK;
+    return launched(e, "gsm_actor_sample launch");
 }
 
 int gsm_actor_eval(const float *x, int64_t x_row_stride, const float *w1, const float *b1, const float *w2,
@@ -1689,14 +1702,13 @@ int gsm_actor_eval(const float *x, int64_t x_row_stride, const float *w1, const 
                    void *stream) {
     if (const int rc = actor_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_actions)) return rc;
     if (n_envs == 0) return GSM_OK;
-    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (const int rc = head_pointers(x, w1, b1, w2, b2, hidden)) return rc;
     if (!actions || !logp) return fail(nullptr, GSM_EINVAL, "actions or logp is NULL");
     gsm::ActorParams p = actor_params(x, x_row_stride, w1, b1, w2, b2, n_envs, n_agents, in_features, n_actions,
                                       status);
     p.actions_in = actions, p.logp = logp, p.entropy = entropy;
     const hipError_t e = gsm::launch_actor_forward(p, hidden, true, as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_eval launch");
-    return GSM_OK;
+    return launched(e, "gsm_actor_eval launch");
 }
 
 int gsm_actor_backward_work_floats(int32_t in_features, int32_t hidden, int32_t n_actions, int64_t *n_floats) {
@@ -1716,22 +1728,20 @@ int gsm_actor_eval_bwd(const float *g_logp, const float *g_ent, const float *x, 
     hipStream_t s = as_stream(stream);
     if (n_envs == 0) {
         const size_t f = sizeof(float);
-        hipError_t e = hipMemsetAsync(dw2, 0, f * n_actions * (hidden ? hidden : in_features), s);
-        if (e == hipSuccess) e = hipMemsetAsync(db2, 0, f * n_actions, s);
-        if (hidden && e == hipSuccess) e = hipMemsetAsync(dw1, 0, f * hidden * in_features, s);
-        if (hidden && e == hipSuccess) e = hipMemsetAsync(db1, 0, f * hidden, s);
-        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_eval_bwd memset");
-        return GSM_OK;
+        return launched(zero_all({{dw2, f * n_actions * (hidden ? hidden : in_features)},
+                                  {db2, f * n_actions},
+                                  {hidden ? dw1 : nullptr, f * hidden * in_features},
+                                  {hidden ? db1 : nullptr, f * hidden}}, s),
+                        "gsm_actor_eval_bwd memset");
     }
-    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (const int rc = head_pointers(x, w1, b1, w2, b2, hidden)) return rc;
     if (!g_logp || !actions || !work) return fail(nullptr, GSM_EINVAL, "g_logp, actions or work is NULL");
     if ((uintptr_t)dx % 16) return fail(nullptr, GSM_EINVAL, "dx must be 16-byte aligned");
     gsm::ActorParams p = actor_params(x, x_row_stride, w1, b1, w2, b2, n_envs, n_agents, in_features, n_actions,
                                       status);
     p.actions_in = actions, p.g_logp = g_logp, p.g_ent = g_ent, p.dx = dx, p.part = work;
     const hipError_t e = gsm::launch_actor_backward(p, hidden, dw1, db1, dw2, db2, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_actor_eval_bwd launch");
-    return GSM_OK;
+    return launched(e, "gsm_actor_eval_bwd launch");
 }
 
 // the shape limits of the critic head, before anything else is looked at
@@ -1772,14 +1782,13 @@ int gsm_critic_eval(const float *x, int64_t x_row_stride, const int32_t *n_valid
                     void *stream) {
     if (const int rc = critic_shape(x_row_stride, n_envs, n_agents, in_features, hidden, n_out)) return rc;
     if (n_envs == 0) return GSM_OK;
-    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (const int rc = head_pointers(x, w1, b1, w2, b2, hidden)) return rc;
     if (!values) return fail(nullptr, GSM_EINVAL, "values is NULL");
     gsm::CriticParams p = critic_params(x, x_row_stride, n_valid, w1, b1, w2, b2, n_envs, n_agents, in_features,
                                         n_out, status);
     p.denorm = denorm, p.values = values;
     const hipError_t e = gsm::launch_critic_forward(p, hidden, as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_critic_eval launch");
-    return GSM_OK;
+    return launched(e, "gsm_critic_eval launch");
 }
 
 int gsm_critic_backward_work_floats(int32_t in_features, int32_t hidden, int32_t n_out, int64_t *n_floats) {
@@ -1798,22 +1807,18 @@ int gsm_critic_eval_bwd(const float *g, const float *x, int64_t x_row_stride, co
     hipStream_t s = as_stream(stream);
     if (n_envs == 0) {
         const size_t f = sizeof(float);
-        hipError_t e = hipMemsetAsync(dw2, 0, f * n_out * hidden, s);
-        if (e == hipSuccess) e = hipMemsetAsync(db2, 0, f * n_out, s);
-        if (e == hipSuccess) e = hipMemsetAsync(dw1, 0, f * hidden * 2 * in_features, s);
-        if (e == hipSuccess) e = hipMemsetAsync(db1, 0, f * hidden, s);
-        if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_critic_eval_bwd memset");
-        return GSM_OK;
+        return launched(zero_all({{dw2, f * n_out * hidden}, {db2, f * n_out}, {dw1, f * hidden * 2 * in_features},
+                                  {db1, f * hidden}}, s),
+                        "gsm_critic_eval_bwd memset");
     }
-    if (const int rc = actor_pointers(x, w1, b1, w2, b2, hidden)) return rc;
+    if (const int rc = head_pointers(x, w1, b1, w2, b2, hidden)) return rc;
     if (!g || !work) return fail(nullptr, GSM_EINVAL, "g or work is NULL");
     if ((uintptr_t)dx % 16) return fail(nullptr, GSM_EINVAL, "dx must be 16-byte aligned");
     gsm::CriticParams p = critic_params(x, x_row_stride, n_valid, w1, b1, w2, b2, n_envs, n_agents, in_features,
                                         n_out, status);
     p.g = g, p.dx = dx, p.part = work;
     const hipError_t e = gsm::launch_critic_backward(p, hidden, dw1, db1, dw2, db2, s);
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_critic_eval_bwd launch");
-    return GSM_OK;
+    return launched(e, "gsm_critic_eval_bwd launch");
 }
 
 int gsm_ppo_loss_work_floats(int64_t n_rows, int64_t *n_floats) {
@@ -1852,8 +1857,7 @@ int gsm_ppo_loss(const float *logp, const float *ent, const float *values, const
     p.g_logp = g_logp, p.g_ent = g_ent, p.g_values = g_values;
     p.status = status;
     const hipError_t e = gsm::launch_ppo_loss(p, as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_ppo_loss launch");
-    return GSM_OK;
+    return launched(e, "gsm_ppo_loss launch");
 }
 
 int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,
@@ -1865,8 +1869,7 @@ int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_
     if (!reward || !value || !done || !ret) return fail(nullptr, GSM_EINVAL, "a required pointer is NULL");
     const hipError_t e = gsm::launch_gae(reward, value, done, n_steps, n_envs, n_agents, gamma, gamma_lambda, ret,
                                          as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_gae launch");
-    return GSM_OK;
+    return launched(e, "gsm_gae launch");
 }
 
 int gsm_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,
@@ -1889,8 +1892,7 @@ int gsm_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const
                                             env_ids, n_frames, half_width, agent_size, target_size,
                                             obstacle_size, width, height, edges ? 1 : 0, rgba,
                                             as_stream(stream));
-    if (e != hipSuccess) return hip_fail(nullptr, e, "gsm_render launch");
-    return GSM_OK;
+    return launched(e, "gsm_render launch");
 }
 
 int gsm_debug_set_stamps(gsm_handle *h, void *stamps) {

@@ -22,16 +22,16 @@
 // [h | 1] and dW1|db1 = dh^T [x | 1], from LDS with a 4x4 register tile per
 // thread, each tile's products added by their owning thread to the workgroup's
 // partial in `work` (a few KB that stay in L2, so no accumulator is held over
-// the per-row part); gsm_actor_bwd_sum_kernel adds the partials in a fixed
-// order. No float atomics.
+// the per-row part); gsm_partial_sum_kernel adds the partials in a fixed
+// order. No float atomics. The MLP pieces are gsm_mlp.h's, shared with the
+// critic head.
 #pragma once
-#include "gsm.h"
-#include "gsm_device.h"
+#include "gsm_mlp.h"
 #include "gsm_philox.h"
 
 namespace gsm {
 
-constexpr int kActorThreads = 128;       // = rows of a tile
+constexpr int kActorThreads = kMlpThreads;
 constexpr int kActorMaxActions = 8;
 constexpr int kActorFwdMaxBlocks = 2048;
 constexpr int kActorBwdMaxBlocks = 512;  // two per CU: the size of `work`
@@ -60,33 +60,16 @@ __host__ __device__ inline ActorLds actor_lds(int in, int kH, bool bwd) {
     return L;
 }
 
-// the weights into LDS (scalar loads: no alignment asked of them); the rows of
-// w2 / b2 past n_actions are zeros
+// the weights into LDS: W1^T [in][kH], w2 / b2 padded to eight rows
 template <int kH>
 __device__ __forceinline__ void actor_load_weights(const ActorParams &p, const ActorLds &L, float *sm) {
-    const int tid = threadIdx.x;
-    if (kH) {
-        for (int i = tid; i < kH * p.in; i += kActorThreads) {   // transposed: [in][kH]
-            const int j = i / p.in, k = i - j * p.in;
-            sm[L.w1 + k * kH + j] = p.w1[i];
-        }
-        for (int i = tid; i < kH; i += kActorThreads) sm[L.b1 + i] = p.b1[i];
-    }
-    for (int i = tid; i < kActorMaxActions * L.KW; i += kActorThreads)
-        sm[L.w2 + i] = i < p.nA * L.KW ? p.w2[i] : 0.0f;
-    for (int i = tid; i < kActorMaxActions; i += kActorThreads) sm[L.b2 + i] = i < p.nA ? p.b2[i] : 0.0f;
+    mlp_load_weights<kH, kActorMaxActions>(p.w1, p.b1, p.w2, p.b2, p.in, L.KW, p.nA, sm + L.w1, sm + L.b1, sm + L.w2,
+                                           sm + L.b2);
 }
 
-// rows [row0, row0 + 128) of x into the tile, zeros past R, the pad (1, 0, 0, 0)
+// rows [row0, row0 + 128) of x into the tile, zeros past R
 __device__ __forceinline__ void actor_load_tile(const ActorParams &p, const ActorLds &L, float *sm, int64_t row0) {
-    const int n4 = p.in >> 2, per = n4 + 1;
-    for (int i = threadIdx.x; i < kActorThreads * per; i += kActorThreads) {
-        const int row = i / per, c4 = i - row * per;
-        float4 v = make_float4(c4 < n4 ? 0.0f : 1.0f, 0.0f, 0.0f, 0.0f);
-        if (c4 < n4 && row0 + row < p.R)
-            v = *reinterpret_cast<const float4 *>(p.x + (row0 + row) * p.x_stride + 4 * c4);
-        *reinterpret_cast<float4 *>(sm + L.xs + row * L.XS + 4 * c4) = v;
-    }
+    mlp_load_tile(p.x, p.x_stride, row0, p.in >> 2, sm + L.xs, L.XS, [&](int row) { return row0 + row < p.R; });
 }
 
 struct ActorRow {
@@ -106,40 +89,8 @@ __device__ __forceinline__ void actor_head(const float *__restrict__ xr, const f
     if constexpr (kH > 0) {
 #pragma unroll
         for (int j = 0; j < kH; ++j) h[j] = sm[L.b1 + j];
-#pragma unroll 1
-        for (int k4 = 0; k4 < n4; ++k4) {
-            const float4 xv = *reinterpret_cast<const float4 *>(xr + 4 * k4);
-            const float xk[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {   // input 4 k4 + kk into every h[j]: 16-byte reads of four j
-                const float *wk = sm + L.w1 + (4 * k4 + kk) * kH;
-#pragma unroll
-                for (int j4 = 0; j4 < kH / 4; ++j4) {
-                    const float4 w = *reinterpret_cast<const float4 *>(wk + 4 * j4);
-                    h[4 * j4] = fmaf(w.x, xk[kk], h[4 * j4]);
-                    h[4 * j4 + 1] = fmaf(w.y, xk[kk], h[4 * j4 + 1]);
-                    h[4 * j4 + 2] = fmaf(w.z, xk[kk], h[4 * j4 + 2]);
-                    h[4 * j4 + 3] = fmaf(w.w, xk[kk], h[4 * j4 + 3]);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kH; ++j) h[j] = h[j] < 0.0f ? 0.0f : h[j];   // a NaN stays a NaN
-        // all eight chains side by side (the rows of w2 past n_actions are zeros and their
-        // logits are never looked at)
-#pragma unroll
-        for (int a = 0; a < kActorMaxActions; ++a) o.l[a] = sm[L.b2 + a];
-#pragma unroll
-        for (int j4 = 0; j4 < kH / 4; ++j4) {
-#pragma unroll
-            for (int a = 0; a < kActorMaxActions; ++a) {
-                const float4 w = *reinterpret_cast<const float4 *>(sm + L.w2 + a * kH + 4 * j4);
-                o.l[a] = fmaf(w.x, h[4 * j4], o.l[a]);
-                o.l[a] = fmaf(w.y, h[4 * j4 + 1], o.l[a]);
-                o.l[a] = fmaf(w.z, h[4 * j4 + 2], o.l[a]);
-                o.l[a] = fmaf(w.w, h[4 * j4 + 3], o.l[a]);
-            }
-        }
+        mlp_hidden<kH>(xr, sm + L.w1, n4, h);
+        mlp_output<kH, kActorMaxActions>(sm + L.w2, sm + L.b2, h, o.l);
     } else {
 #pragma unroll
         for (int a = 0; a < kActorMaxActions; ++a) o.l[a] = sm[L.b2 + a];
@@ -264,41 +215,6 @@ __global__ __launch_bounds__(kActorThreads) void gsm_actor_fwd_kernel(const Acto
     }
 }
 
-// acc[i][.] += a[i] * b[.]: one row's contribution to a 4x4 tile of A^T B
-__device__ __forceinline__ void actor_outer(float4 (&acc)[4], const float4 a, const float4 b) {
-    acc[0].x = fmaf(a.x, b.x, acc[0].x), acc[0].y = fmaf(a.x, b.y, acc[0].y);
-    acc[0].z = fmaf(a.x, b.z, acc[0].z), acc[0].w = fmaf(a.x, b.w, acc[0].w);
-    acc[1].x = fmaf(a.y, b.x, acc[1].x), acc[1].y = fmaf(a.y, b.y, acc[1].y);
-    acc[1].z = fmaf(a.y, b.z, acc[1].z), acc[1].w = fmaf(a.y, b.w, acc[1].w);
-    acc[2].x = fmaf(a.z, b.x, acc[2].x), acc[2].y = fmaf(a.z, b.y, acc[2].y);
-    acc[2].z = fmaf(a.z, b.z, acc[2].z), acc[2].w = fmaf(a.z, b.w, acc[2].w);
-    acc[3].x = fmaf(a.w, b.x, acc[3].x), acc[3].y = fmaf(a.w, b.y, acc[3].y);
-    acc[3].z = fmaf(a.w, b.z, acc[3].z), acc[3].w = fmaf(a.w, b.w, acc[3].w);
-}
-
-// One 4x4 tile of a gradient block into the workgroup's partial: rows
-// m0..m0+3 (< n_rows), columns c4*4.. of `mat` ([n_rows][n_cols]) or, for the
-// pad column block (c4 == n_cols / 4), its first column into `bias`. The first
-// tile of rows sets the partial, the later ones add to it (the same thread
-// owns the same entries every time).
-__device__ __forceinline__ void actor_add_tile(const float4 (&acc)[4], int m0, int c4, int n_rows, int n_cols,
-                                               float *mat, float *bias, bool first) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + i;
-        if (m >= n_rows) continue;
-        if (4 * c4 < n_cols) {
-            float *d = mat + m * n_cols + 4 * c4;
-            d[0] = first ? acc[i].x : d[0] + acc[i].x;
-            d[1] = first ? acc[i].y : d[1] + acc[i].y;
-            d[2] = first ? acc[i].z : d[2] + acc[i].z;
-            d[3] = first ? acc[i].w : d[3] + acc[i].w;
-        } else {
-            bias[m] = first ? acc[i].x : bias[m] + acc[i].x;
-        }
-    }
-}
-
 // a partial: dw1 [kH][in], db1 [kH], dw2 [nA][KW], db2 [nA]
 __host__ __device__ inline int actor_partial_floats(int in, int kH, int nA) {
     return kH * in + kH + nA * (kH ? kH : in) + nA;
@@ -354,28 +270,8 @@ __global__ __launch_bounds__(kActorThreads) void gsm_actor_bwd_kernel(const Acto
         *reinterpret_cast<float4 *>(sm + L.ds + tid * 8 + 4) = make_float4(dl[4], dl[5], dl[6], dl[7]);
         const int64_t r = row0 + tid;
         if constexpr (kH > 0) {
-            float *hr = sm + L.hs + tid * L.HS;
-#pragma unroll
-            for (int j4 = 0; j4 < kH / 4; ++j4)
-                *reinterpret_cast<float4 *>(hr + 4 * j4) = make_float4(h[4 * j4], h[4 * j4 + 1], h[4 * j4 + 2],
-                                                                       h[4 * j4 + 3]);
-            *reinterpret_cast<float4 *>(hr + kH) = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-            // dh = W2^T dlogit where h > 0, in h's registers
-#pragma unroll
-            for (int j4 = 0; j4 < kH / 4; ++j4) {
-                float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-                for (int a = 0; a < kActorMaxActions; ++a)
-                    if (a < nA) {
-                        const float4 w = *reinterpret_cast<const float4 *>(sm + L.w2 + a * kH + 4 * j4);
-                        d.x = fmaf(w.x, dl[a], d.x), d.y = fmaf(w.y, dl[a], d.y);
-                        d.z = fmaf(w.z, dl[a], d.z), d.w = fmaf(w.w, dl[a], d.w);
-                    }
-                h[4 * j4] = h[4 * j4] > 0.0f ? d.x : 0.0f;
-                h[4 * j4 + 1] = h[4 * j4 + 1] > 0.0f ? d.y : 0.0f;
-                h[4 * j4 + 2] = h[4 * j4 + 2] > 0.0f ? d.z : 0.0f;
-                h[4 * j4 + 3] = h[4 * j4 + 3] > 0.0f ? d.w : 0.0f;
-            }
+            mlp_store_row<kH, true>(sm + L.hs + tid * L.HS, h);
+            mlp_hidden_grad<kH, kActorMaxActions>(sm + L.w2, dl, nA, h);
         } else {
             if (p.dx && r < p.R)
                 for (int k4 = 0; k4 < n4; ++k4) {
@@ -397,101 +293,33 @@ __global__ __launch_bounds__(kActorThreads) void gsm_actor_bwd_kernel(const Acto
             const float *sb = kH ? sm + L.hs + 4 * c4 : sm + L.xs + 4 * c4;
             const int SB = kH ? L.HS : L.XS;
             float4 acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll 4
-            for (int row = 0; row < kActorThreads; ++row)
-                actor_outer(acc, *reinterpret_cast<const float4 *>(sa + row * 8),
-                            *reinterpret_cast<const float4 *>(sb + row * SB));
-            actor_add_tile(acc, 4 * a4, c4, nA, kH ? kH : in, pw2, pb2, first);
+            mlp_gemm_tile(acc, sa, 8, sb, SB, kActorThreads);
+            mlp_add_tile(acc, 4 * a4, c4, nA, kH ? kH : in, pw2, pb2, first);
         }
         if constexpr (kH > 0) {
             __syncthreads();   // h has been read: dh takes its place
             float *hr = sm + L.hs + tid * L.HS;
-#pragma unroll
-            for (int j4 = 0; j4 < kH / 4; ++j4)
-                *reinterpret_cast<float4 *>(hr + 4 * j4) = make_float4(h[4 * j4], h[4 * j4 + 1], h[4 * j4 + 2],
-                                                                       h[4 * j4 + 3]);
+            mlp_store_row<kH, false>(hr, h);
             // dx = W1^T dh, the row's dh read back from LDS (the thread's own stores) so that
             // this loop is not unrolled over h's registers
             if (p.dx && r < p.R)
-                for (int k4 = 0; k4 < n4; ++k4) {
-                    float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 2
-                    for (int j4 = 0; j4 < kH / 4; ++j4) {
-                        const float4 g = *reinterpret_cast<const float4 *>(hr + 4 * j4);
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) {
-                            const float4 w =
-                                *reinterpret_cast<const float4 *>(sm + L.w1 + (4 * k4 + kk) * kH + 4 * j4);
-                            d[kk] = fmaf(w.x, g.x, d[kk]);
-                            d[kk] = fmaf(w.y, g.y, d[kk]);
-                            d[kk] = fmaf(w.z, g.z, d[kk]);
-                            d[kk] = fmaf(w.w, g.w, d[kk]);
-                        }
-                    }
-                    *reinterpret_cast<float4 *>(p.dx + r * in + 4 * k4) = make_float4(d[0], d[1], d[2], d[3]);
-                }
+                for (int k4 = 0; k4 < n4; ++k4)
+                    *reinterpret_cast<float4 *>(p.dx + r * in + 4 * k4) =
+                        mlp_dx_group<kH>(sm + L.w1 + 4 * k4 * kH, hr);
             __syncthreads();
             for (int item = tid; item < n_items1; item += kActorThreads) {
                 const int j4 = item / per1, c4 = item - j4 * per1;
                 const float *sa = sm + L.hs + 4 * j4, *sb = sm + L.xs + 4 * c4;
                 float4 acc[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll 4
-                for (int row = 0; row < kActorThreads; ++row)
-                    actor_outer(acc, *reinterpret_cast<const float4 *>(sa + row * L.HS),
-                                *reinterpret_cast<const float4 *>(sb + row * L.XS));
-                actor_add_tile(acc, 4 * j4, c4, kH, in, pw1, pb1, first);
+                mlp_gemm_tile(acc, sa, L.HS, sb, L.XS, kActorThreads);
+                mlp_add_tile(acc, 4 * j4, c4, kH, in, pw1, pb1, first);
             }
         }
-    }
-}
-// partials -> dw1 | db1 | dw2 | db2 (contiguous in a partial, four outputs):
-// gsm_env_conv_bwd_sum_kernel's scheme, a fixed order for a given shape
-__global__ __launch_bounds__(64 * kBwdSumRows) void gsm_actor_bwd_sum_kernel(const float *__restrict__ part,
-                                                                             int n_part, int P, int o_b1, int o_w2,
-                                                                             int o_b2, float *__restrict__ dw1,
-                                                                             float *__restrict__ db1,
-                                                                             float *__restrict__ dw2,
-                                                                             float *__restrict__ db2) {
-    __shared__ float red[kBwdSumRows][64];
-    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    float sum = 0.0f;
-    if (c < P)
-        for (int b = r; b < n_part; b += 8 * kBwdSumRows) {
-            float x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int bu = b + u * kBwdSumRows;
-                x[u] = bu < n_part ? part[(int64_t)bu * P + c] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += x[u];
-        }
-    red[r][lane] = sum;
-    __syncthreads();
-    if (r == 0 && c < P) {
-        float tot = 0.0f;
-        for (int i = 0; i < kBwdSumRows; ++i) tot += red[i][lane];
-        if (c < o_b1) dw1[c] = tot;
-        else if (c < o_w2) db1[c - o_b1] = tot;
-        else if (c < o_b2) dw2[c - o_w2] = tot;
-        else db2[c - o_b2] = tot;
     }
 }
 
 int64_t actor_backward_work_floats(int in, int hidden, int nA) {
     return (int64_t)kActorBwdMaxBlocks * actor_partial_floats(in, hidden, nA);
-}
-
-template <class K>
-static hipError_t actor_lds_attr(K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds);
 }
 
 hipError_t launch_actor_forward(const ActorParams &p, int hidden, bool eval, hipStream_t s) {
@@ -500,23 +328,12 @@ hipError_t launch_actor_forward(const ActorParams &p, int hidden, bool eval, hip
     const int n_tiles = (p.R + kActorThreads - 1) / kActorThreads;
     const unsigned blocks = (unsigned)(n_tiles < kActorFwdMaxBlocks ? n_tiles : kActorFwdMaxBlocks);
     (void)hipGetLastError();
-#define GSM_ACTOR_FWD(H)                                                                   \
-    do {                                                                                   \
-        hipError_t e = eval ? actor_lds_attr(gsm_actor_fwd_kernel<H, true>, lds)           \
-                            : actor_lds_attr(gsm_actor_fwd_kernel<H, false>, lds);         \
-        if (e != hipSuccess) return e;                                                     \
-        if (eval) gsm_actor_fwd_kernel<H, true><<<blocks, kActorThreads, lds, s>>>(p);     \
-        else gsm_actor_fwd_kernel<H, false><<<blocks, kActorThreads, lds, s>>>(p);         \
-    } while (0)
-    switch (hidden) {
-        case 0: GSM_ACTOR_FWD(0); break;
-        case 16: GSM_ACTOR_FWD(16); break;
-        case 32: GSM_ACTOR_FWD(32); break;
-        case 64: GSM_ACTOR_FWD(64); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GSM_ACTOR_FWD
-    return hipGetLastError();
+    const hipError_t e = mlp_dispatch_hidden<true>(hidden, [&](auto H) {
+        constexpr int kH = decltype(H)::value;
+        return eval ? mlp_launch(gsm_actor_fwd_kernel<kH, true>, blocks, lds, p, s)
+                    : mlp_launch(gsm_actor_fwd_kernel<kH, false>, blocks, lds, p, s);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_actor_backward(const ActorParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
@@ -526,24 +343,15 @@ hipError_t launch_actor_backward(const ActorParams &p, int hidden, float *dw1, f
     const int n_tiles = (p.R + kActorThreads - 1) / kActorThreads;
     const unsigned blocks = (unsigned)(n_tiles < kActorBwdMaxBlocks ? n_tiles : kActorBwdMaxBlocks);
     (void)hipGetLastError();
-#define GSM_ACTOR_BWD(H)                                                          \
-    do {                                                                          \
-        const hipError_t e = actor_lds_attr(gsm_actor_bwd_kernel<H>, lds);        \
-        if (e != hipSuccess) return e;                                            \
-        gsm_actor_bwd_kernel<H><<<blocks, kActorThreads, lds, s>>>(p);            \
-    } while (0)
-    switch (hidden) {
-        case 0: GSM_ACTOR_BWD(0); break;
-        case 16: GSM_ACTOR_BWD(16); break;
-        case 32: GSM_ACTOR_BWD(32); break;
-        case 64: GSM_ACTOR_BWD(64); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GSM_ACTOR_BWD
-    const int P = actor_partial_floats(p.in, hidden, p.nA);
-    const int o_b1 = hidden * p.in, o_w2 = o_b1 + hidden, o_b2 = o_w2 + p.nA * (hidden ? hidden : p.in);
-    gsm_actor_bwd_sum_kernel<<<(unsigned)((P + 63) / 64), 64 * kBwdSumRows, 0, s>>>(p.part, (int)blocks, P, o_b1,
-                                                                                   o_w2, o_b2, dw1, db1, dw2, db2);
+    const hipError_t e = mlp_dispatch_hidden<true>(hidden, [&](auto H) {
+        return mlp_launch(gsm_actor_bwd_kernel<decltype(H)::value>, blocks, lds, p, s);
+    });
+    if (e != hipSuccess) return e;
+    // a partial is dw1 | db1 | dw2 | db2, contiguous
+    launch_partial_sum(p.part, (int)blocks, {{hidden * p.in, dw1},
+                                            {hidden, db1},
+                                            {p.nA * (hidden ? hidden : p.in), dw2},
+                                            {p.nA, db2}}, s);
     return hipGetLastError();
 }
 

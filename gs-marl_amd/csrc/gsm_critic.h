@@ -21,13 +21,13 @@
 //
 // Backward: dv, h and then dh go through LDS; dW2|db2 = dv^T [h | 1] and
 // dW1[:, in:]|db1 = dh^T [x | 1] are the actor's small GEMMs over the tile's
-// rows (actor_outer / actor_add_tile, a 4x4 register tile per thread added to
+// rows (mlp_gemm_tile / mlp_add_tile, a 4x4 register tile per thread added to
 // the workgroup's partial in `work` tile by tile, so no accumulator is held
 // over the per-row part); the pool path adds s_b = sum_i dh_{b,i} (env task,
 // ascending agent), dW1[:, :in] = s^T pool (a GEMM over the tile's envs) and
 // dpool_b = W1[:, :in]^T s_b, whose quotient by n_b every row of the env adds
-// to its dx. gsm_actor_bwd_sum_kernel adds the partials in a fixed order. No
-// float atomics.
+// to its dx. gsm_partial_sum_kernel adds the partials in a fixed order. No
+// float atomics. The MLP pieces are gsm_mlp.h's, shared with the actor head.
 #pragma once
 #include "gsm_actor.h"
 
@@ -71,18 +71,11 @@ __host__ __device__ inline CriticLds critic_lds(int in, int kH, int ept, bool bw
     return L;
 }
 
-// the weights into LDS (scalar loads: no alignment asked of them); W1 transposed
-// to [2 in][kH], the rows of w2 / b2 past n_out zeros
+// the weights into LDS: W1^T [2 in][kH], w2 / b2 padded to two rows
 template <int kH>
 __device__ __forceinline__ void critic_load_weights(const CriticParams &p, const CriticLds &L, float *sm) {
-    const int tid = threadIdx.x, in2 = 2 * p.in;
-    for (int i = tid; i < kH * in2; i += kActorThreads) {
-        const int j = i / in2, k = i - j * in2;
-        sm[L.w1 + k * kH + j] = p.w1[i];
-    }
-    for (int i = tid; i < kH; i += kActorThreads) sm[L.b1 + i] = p.b1[i];
-    for (int i = tid; i < kCriticMaxOut * kH; i += kActorThreads) sm[L.w2 + i] = i < p.nO * kH ? p.w2[i] : 0.0f;
-    for (int i = tid; i < 4; i += kActorThreads) sm[L.b2 + i] = i < p.nO ? p.b2[i] : 0.0f;
+    mlp_load_weights<kH, kCriticMaxOut>(p.w1, p.b1, p.w2, p.b2, 2 * p.in, kH, p.nO, sm + L.w1, sm + L.b1, sm + L.w2,
+                                        sm + L.b2);
 }
 
 // The tile of envs [env0, env0 + ept): the clamped agent counts, the x rows
@@ -92,7 +85,7 @@ __device__ __forceinline__ void critic_load_weights(const CriticParams &p, const
 template <int kH>
 __device__ __forceinline__ void critic_load_tile(const CriticParams &p, const CriticLds &L, float *sm, int ept,
                                                  int64_t env0) {
-    const int tid = threadIdx.x, N = p.n_agents, in = p.in, n4 = in >> 2, per = n4 + 1;
+    const int tid = threadIdx.x, N = p.n_agents, in = p.in, n4 = in >> 2;
     int *cnt = reinterpret_cast<int *>(sm + L.cnt);
     __syncthreads();
     if (tid < ept) {
@@ -107,15 +100,10 @@ __device__ __forceinline__ void critic_load_tile(const CriticParams &p, const Cr
         cnt[tid] = n;
     }
     __syncthreads();
-    const int64_t row0 = env0 * N;
-    for (int i = tid; i < kActorThreads * per; i += kActorThreads) {
-        const int row = i / per, c4 = i - row * per;
+    mlp_load_tile(p.x, p.x_stride, env0 * N, n4, sm + L.xs, L.XS, [&](int row) {
         const int e = row / N, a = row - e * N;
-        float4 v = make_float4(c4 < n4 ? 0.0f : 1.0f, 0.0f, 0.0f, 0.0f);
-        if (c4 < n4 && e < ept && a < cnt[e])
-            v = *reinterpret_cast<const float4 *>(p.x + (row0 + row) * p.x_stride + 4 * c4);
-        *reinterpret_cast<float4 *>(sm + L.xs + row * L.XS + 4 * c4) = v;
-    }
+        return e < ept && a < cnt[e];
+    });
     __syncthreads();
     // pool_b = (x_{b,0} + x_{b,1} + ..) / n_b over the valid agents, ascending
     for (int t = tid; t < ept * n4; t += kActorThreads) {
@@ -152,36 +140,17 @@ __device__ __forceinline__ void critic_load_tile(const CriticParams &p, const Cr
 }
 
 // h of one row: the chain continued from its env's prefix cb over the x half
-// of W1 (actor_head's loop), then relu
+// of W1 (the actor's loop), then relu
 template <int kH>
 __device__ __forceinline__ void critic_hidden(const float *__restrict__ xr, const float *__restrict__ cb,
                                               const float *__restrict__ sm, const CriticLds &L, int in,
                                               float (&h)[kH]) {
-    const int n4 = in >> 2;
 #pragma unroll
     for (int j4 = 0; j4 < kH / 4; ++j4) {
         const float4 c = *reinterpret_cast<const float4 *>(cb + 4 * j4);
         h[4 * j4] = c.x, h[4 * j4 + 1] = c.y, h[4 * j4 + 2] = c.z, h[4 * j4 + 3] = c.w;
     }
-#pragma unroll 1
-    for (int k4 = 0; k4 < n4; ++k4) {
-        const float4 xv = *reinterpret_cast<const float4 *>(xr + 4 * k4);
-        const float xk[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const float *wk = sm + L.w1 + (in + 4 * k4 + kk) * kH;
-#pragma unroll
-            for (int j4 = 0; j4 < kH / 4; ++j4) {
-                const float4 w = *reinterpret_cast<const float4 *>(wk + 4 * j4);
-                h[4 * j4] = fmaf(w.x, xk[kk], h[4 * j4]);
-                h[4 * j4 + 1] = fmaf(w.y, xk[kk], h[4 * j4 + 1]);
-                h[4 * j4 + 2] = fmaf(w.z, xk[kk], h[4 * j4 + 2]);
-                h[4 * j4 + 3] = fmaf(w.w, xk[kk], h[4 * j4 + 3]);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < kH; ++j) h[j] = h[j] < 0.0f ? 0.0f : h[j];   // a NaN stays a NaN
+    mlp_hidden<kH>(xr, sm + L.w1 + in * kH, in >> 2, h);
 }
 
 template <int kH>
@@ -208,19 +177,7 @@ __global__ __launch_bounds__(kActorThreads) void gsm_critic_fwd_kernel(const Cri
         float h[kH];
         critic_hidden<kH>(sm + L.xs + tid * L.XS, sm + L.c + e * L.CS, sm, L, p.in, h);
         float v[kCriticMaxOut];
-#pragma unroll
-        for (int o = 0; o < kCriticMaxOut; ++o) v[o] = sm[L.b2 + o];
-#pragma unroll
-        for (int j4 = 0; j4 < kH / 4; ++j4) {
-#pragma unroll
-            for (int o = 0; o < kCriticMaxOut; ++o) {
-                const float4 w = *reinterpret_cast<const float4 *>(sm + L.w2 + o * kH + 4 * j4);
-                v[o] = fmaf(w.x, h[4 * j4], v[o]);
-                v[o] = fmaf(w.y, h[4 * j4 + 1], v[o]);
-                v[o] = fmaf(w.z, h[4 * j4 + 2], v[o]);
-                v[o] = fmaf(w.w, h[4 * j4 + 3], v[o]);
-            }
-        }
+        mlp_output<kH, kCriticMaxOut>(sm + L.w2, sm + L.b2, h, v);
         const bool valid = a < cnt[e];
         const int64_t r = (env0 + e) * N + a;
         bool fin = true;
@@ -273,48 +230,22 @@ __global__ __launch_bounds__(kActorThreads) void gsm_critic_bwd_kernel(const Cri
         for (int o = 0; o < kCriticMaxOut; ++o) dv[o] = (valid && o < nO) ? p.g[(int64_t)o * p.R + r] : 0.0f;
         *reinterpret_cast<float4 *>(sm + L.ds + tid * 4) = make_float4(dv[0], dv[1], 0.0f, 0.0f);
         float *hr = sm + L.hs + tid * L.HS;
+        // a row that is no valid agent's takes no part: h = 0, dh = 0
+        if (!valid) {
 #pragma unroll
-        for (int j4 = 0; j4 < kH / 4; ++j4) {
-            // a row that is no valid agent's takes no part: h = 0, dh = 0
-            if (!valid) h[4 * j4] = h[4 * j4 + 1] = h[4 * j4 + 2] = h[4 * j4 + 3] = 0.0f;
-            *reinterpret_cast<float4 *>(hr + 4 * j4) = make_float4(h[4 * j4], h[4 * j4 + 1], h[4 * j4 + 2],
-                                                                   h[4 * j4 + 3]);
+            for (int j = 0; j < kH; ++j) h[j] = 0.0f;
         }
-        *reinterpret_cast<float4 *>(hr + kH) = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-        // dh = W2^T dv where h > 0, in h's registers
-#pragma unroll
-        for (int j4 = 0; j4 < kH / 4; ++j4) {
-            float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-            for (int o = 0; o < kCriticMaxOut; ++o)
-                if (o < nO) {
-                    const float4 w = *reinterpret_cast<const float4 *>(sm + L.w2 + o * kH + 4 * j4);
-                    d.x = fmaf(w.x, dv[o], d.x), d.y = fmaf(w.y, dv[o], d.y);
-                    d.z = fmaf(w.z, dv[o], d.z), d.w = fmaf(w.w, dv[o], d.w);
-                }
-            h[4 * j4] = h[4 * j4] > 0.0f ? d.x : 0.0f;
-            h[4 * j4 + 1] = h[4 * j4 + 1] > 0.0f ? d.y : 0.0f;
-            h[4 * j4 + 2] = h[4 * j4 + 2] > 0.0f ? d.z : 0.0f;
-            h[4 * j4 + 3] = h[4 * j4 + 3] > 0.0f ? d.w : 0.0f;
-        }
+        mlp_store_row<kH, true>(hr, h);
+        mlp_hidden_grad<kH, kCriticMaxOut>(sm + L.w2, dv, nO, h);
         __syncthreads();   // dv and h of every row are in LDS
         const bool first = tile == (int64_t)blockIdx.x;
         if (tid < per2) {
-            const float *sa = sm + L.ds, *sb = sm + L.hs + 4 * tid;
             float4 acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll 4
-            for (int row = 0; row < kActorThreads; ++row)
-                actor_outer(acc, *reinterpret_cast<const float4 *>(sa + row * 4),
-                            *reinterpret_cast<const float4 *>(sb + row * L.HS));
-            actor_add_tile(acc, 0, tid, nO, kH, pw2, pb2, first);
+            mlp_gemm_tile(acc, sm + L.ds, 4, sm + L.hs + 4 * tid, L.HS, kActorThreads);
+            mlp_add_tile(acc, 0, tid, nO, kH, pw2, pb2, first);
         }
         __syncthreads();   // h has been read: dh takes its place
-#pragma unroll
-        for (int j4 = 0; j4 < kH / 4; ++j4)
-            *reinterpret_cast<float4 *>(hr + 4 * j4) = make_float4(h[4 * j4], h[4 * j4 + 1], h[4 * j4 + 2],
-                                                                   h[4 * j4 + 3]);
+        mlp_store_row<kH, false>(hr, h);
         __syncthreads();
         // s_b = dh_{b,0} + dh_{b,1} + .. over the env's valid agents, ascending
         for (int t = tid; t < ept * (kH / 4); t += kActorThreads) {
@@ -333,73 +264,35 @@ __global__ __launch_bounds__(kActorThreads) void gsm_critic_bwd_kernel(const Cri
         if (p.dx)
             for (int t = tid; t < ept * n4; t += kActorThreads) {
                 const int eb = t / n4, k4 = t - eb * n4, n = cnt[eb];
-                const float *se = sm + L.s + eb * kH;
-                float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 2
-                for (int j4 = 0; j4 < kH / 4; ++j4) {
-                    const float4 g = *reinterpret_cast<const float4 *>(se + 4 * j4);
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        const float4 w = *reinterpret_cast<const float4 *>(sm + L.w1 + (4 * k4 + kk) * kH + 4 * j4);
-                        d[kk] = fmaf(w.x, g.x, d[kk]);
-                        d[kk] = fmaf(w.y, g.y, d[kk]);
-                        d[kk] = fmaf(w.z, g.z, d[kk]);
-                        d[kk] = fmaf(w.w, g.w, d[kk]);
-                    }
-                }
+                const float4 d = mlp_dx_group<kH>(sm + L.w1 + 4 * k4 * kH, sm + L.s + eb * kH);
                 const float dn = n > 0 ? (float)n : 1.0f;
                 *reinterpret_cast<float4 *>(sm + L.c + eb * L.CS + 4 * k4) =
-                    make_float4(d[0] / dn, d[1] / dn, d[2] / dn, d[3] / dn);
+                    make_float4(d.x / dn, d.y / dn, d.z / dn, d.w / dn);
             }
         __syncthreads();
         // dx = W1[:, in:]^T dh + dpool / n_b, the row's dh read back from LDS (the thread's own
         // stores) so that this loop is not unrolled over h's registers; a padded row gets zeros
         if (p.dx && active)
             for (int k4 = 0; k4 < n4; ++k4) {
-                float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 2
-                for (int j4 = 0; j4 < kH / 4; ++j4) {
-                    const float4 g = *reinterpret_cast<const float4 *>(hr + 4 * j4);
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk) {
-                        const float4 w =
-                            *reinterpret_cast<const float4 *>(sm + L.w1 + (in + 4 * k4 + kk) * kH + 4 * j4);
-                        d[kk] = fmaf(w.x, g.x, d[kk]);
-                        d[kk] = fmaf(w.y, g.y, d[kk]);
-                        d[kk] = fmaf(w.z, g.z, d[kk]);
-                        d[kk] = fmaf(w.w, g.w, d[kk]);
-                    }
-                }
+                const float4 d = mlp_dx_group<kH>(sm + L.w1 + (in + 4 * k4) * kH, hr);
                 const float4 q = *reinterpret_cast<const float4 *>(sm + L.c + e * L.CS + 4 * k4);
-                float4 out = make_float4(d[0] + q.x, d[1] + q.y, d[2] + q.z, d[3] + q.w);
+                float4 out = make_float4(d.x + q.x, d.y + q.y, d.z + q.z, d.w + q.w);
                 if (!valid) out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 *reinterpret_cast<float4 *>(p.dx + r * in + 4 * k4) = out;
             }
         // dW1[:, in:] | db1 = dh^T [x | 1] over the tile's rows, into columns in.. of the partial's rows
         for (int item = tid; item < n_items1; item += kActorThreads) {
             const int j4 = item / per1, c4 = item - j4 * per1;
-            const float *sa = sm + L.hs + 4 * j4, *sb = sm + L.xs + 4 * c4;
             float4 acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll 4
-            for (int row = 0; row < kActorThreads; ++row)
-                actor_outer(acc, *reinterpret_cast<const float4 *>(sa + row * L.HS),
-                            *reinterpret_cast<const float4 *>(sb + row * L.XS));
-            actor_add_tile(acc, 4 * j4, c4 < n4 ? c4 : 2 * n4, kH, 2 * in, pw1 + in, pb1, first);
+            mlp_gemm_tile(acc, sm + L.hs + 4 * j4, L.HS, sm + L.xs + 4 * c4, L.XS, kActorThreads);
+            mlp_add_tile(acc, 4 * j4, c4 < n4 ? c4 : 2 * n4, kH, 2 * in, pw1 + in, pb1, first);
         }
         // dW1[:, :in] = s^T pool over the tile's envs
         for (int item = tid; item < n_items0; item += kActorThreads) {
             const int j4 = item / n4, c4 = item - j4 * n4;
-            const float *sa = sm + L.s + 4 * j4, *sb = sm + L.pool + 4 * c4;
             float4 acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll 4
-            for (int eb = 0; eb < ept; ++eb)
-                actor_outer(acc, *reinterpret_cast<const float4 *>(sa + eb * kH),
-                            *reinterpret_cast<const float4 *>(sb + eb * L.XS));
-            actor_add_tile(acc, 4 * j4, c4, kH, 2 * in, pw1, pb1, first);
+            mlp_gemm_tile(acc, sm + L.s + 4 * j4, kH, sm + L.pool + 4 * c4, L.XS, ept);
+            mlp_add_tile(acc, 4 * j4, c4, kH, 2 * in, pw1, pb1, first);
         }
     }
 }
@@ -423,20 +316,10 @@ hipError_t launch_critic_forward(const CriticParams &p, int hidden, hipStream_t 
     if (lds > (size_t)kActorLdsMax) return hipErrorInvalidValue;
     const unsigned blocks = critic_blocks(p, kCriticFwdMaxBlocks);
     (void)hipGetLastError();
-#define GSM_CRITIC_FWD(H)                                                      \
-    do {                                                                       \
-        const hipError_t e = actor_lds_attr(gsm_critic_fwd_kernel<H>, lds);    \
-        if (e != hipSuccess) return e;                                         \
-        gsm_critic_fwd_kernel<H><<<blocks, kActorThreads, lds, s>>>(p);        \
-    } while (0)
-    switch (hidden) {
-        case 16: GSM_CRITIC_FWD(16); break;
-        case 32: GSM_CRITIC_FWD(32); break;
-        case 64: GSM_CRITIC_FWD(64); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GSM_CRITIC_FWD
-    return hipGetLastError();
+    const hipError_t e = mlp_dispatch_hidden<false>(hidden, [&](auto H) {
+        return mlp_launch(gsm_critic_fwd_kernel<decltype(H)::value>, blocks, lds, p, s);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_critic_backward(const CriticParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
@@ -445,23 +328,13 @@ hipError_t launch_critic_backward(const CriticParams &p, int hidden, float *dw1,
     if (lds > (size_t)kActorLdsMax) return hipErrorInvalidValue;
     const unsigned blocks = critic_blocks(p, kCriticBwdMaxBlocks);
     (void)hipGetLastError();
-#define GSM_CRITIC_BWD(H)                                                      \
-    do {                                                                       \
-        const hipError_t e = actor_lds_attr(gsm_critic_bwd_kernel<H>, lds);    \
-        if (e != hipSuccess) return e;                                         \
-        gsm_critic_bwd_kernel<H><<<blocks, kActorThreads, lds, s>>>(p);        \
-    } while (0)
-    switch (hidden) {
-        case 16: GSM_CRITIC_BWD(16); break;
-        case 32: GSM_CRITIC_BWD(32); break;
-        case 64: GSM_CRITIC_BWD(64); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef GSM_CRITIC_BWD
-    const int P = critic_partial_floats(p.in, hidden, p.nO);
-    const int o_b1 = hidden * 2 * p.in, o_w2 = o_b1 + hidden, o_b2 = o_w2 + p.nO * hidden;
-    gsm_actor_bwd_sum_kernel<<<(unsigned)((P + 63) / 64), 64 * kBwdSumRows, 0, s>>>(p.part, (int)blocks, P, o_b1,
-                                                                                   o_w2, o_b2, dw1, db1, dw2, db2);
+    const hipError_t e = mlp_dispatch_hidden<false>(hidden, [&](auto H) {
+        return mlp_launch(gsm_critic_bwd_kernel<decltype(H)::value>, blocks, lds, p, s);
+    });
+    if (e != hipSuccess) return e;
+    // a partial is dw1 | db1 | dw2 | db2, contiguous
+    launch_partial_sum(p.part, (int)blocks, {{hidden * 2 * p.in, dw1}, {hidden, db1}, {p.nO * hidden, dw2}, {p.nO, db2}},
+                       s);
     return hipGetLastError();
 }
 

@@ -23,6 +23,10 @@
 // shuffles; an online softmax keeps (max, denominator, accumulator) in
 // registers while the row's edges stream through (the next edge's index one
 // iteration ahead), so every k_j / v_j row is read once per edge.
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
+
 #include "gsm.h"
 #include "gsm_device.h"
 
@@ -135,49 +139,71 @@ __global__ __launch_bounds__(256) void gsm_attn_aggregate_kernel(
     }
 }
 
+// The lanes of a node (or output row), for the four launchers below: four
+// channels per lane (16-byte accesses) when every head spans whole lanes and
+// the rows the launcher names are 16-byte aligned, one channel per lane
+// otherwise; lp = the power of two >= HC / vec lanes. ok: a node fits a wave.
+struct Lanes {
+    int lp, vec;
+    bool ok;
+};
+
+static bool aligned16(std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t)p;
+    return bits % 16 == 0;
+}
+
+static Lanes select_lanes(int HC, int C, bool aligned) {
+    const int vec = C % 4 == 0 && HC % 4 == 0 && aligned ? 4 : 1;
+    int lp = 1;
+    while (lp * vec < HC) lp <<= 1;
+    return {lp, vec, lp <= kWave};
+}
+
+// f(integral_constant LP, integral_constant VEC) for the 12 legal pairs
+template <class F>
+static hipError_t dispatch_lanes(const Lanes &l, const F &f) {
+#define GSM_LANES(LP, VEC) \
+    case LP: f(std::integral_constant<int, LP>{}, std::integral_constant<int, VEC>{}); return hipSuccess
+    if (l.vec == 4) {
+        switch (l.lp) {
+            GSM_LANES(1, 4);
+            GSM_LANES(2, 4);
+            GSM_LANES(4, 4);
+            GSM_LANES(8, 4);
+            GSM_LANES(16, 4);
+        }
+    } else {
+        switch (l.lp) {
+            GSM_LANES(1, 1);
+            GSM_LANES(2, 1);
+            GSM_LANES(4, 1);
+            GSM_LANES(8, 1);
+            GSM_LANES(16, 1);
+            GSM_LANES(32, 1);
+            GSM_LANES(64, 1);
+        }
+    }
+#undef GSM_LANES
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_attn_aggregate(const float *q, const float *k, const float *v, const float *edge_w,
                                  const float *w_e, const int64_t *row_ptr, const int32_t *col,
                                  const float *skip, int64_t n_nodes, int HC, int C, float scale, float *out,
                                  float *lse, hipStream_t s) {
-    // four channels per lane (16-byte gathers) when every head spans whole
-    // lanes and the rows are 16-byte aligned; one channel per lane otherwise
-    const bool vec4 = C % 4 == 0 && HC % 4 == 0 && ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v |
-                                                     (uintptr_t)out | (uintptr_t)(skip ? skip : out) |
-                                                     (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
-    const int vec = vec4 ? 4 : 1;
-    int lp = 1;
-    while (lp * vec < HC) lp <<= 1;
-    if (lp > kWave) return hipErrorInvalidValue;
-    const int npw = kWave / lp;
+    const Lanes l = select_lanes(HC, C, aligned16({q, k, v, out, skip, w_e}));
+    if (!l.ok) return hipErrorInvalidValue;
+    const int npw = kWave / l.lp;
     const int64_t waves = (n_nodes + npw - 1) / npw;
     const unsigned blocks = (unsigned)((waves + 3) / 4);
     (void)hipGetLastError();
-#define GSM_ATTN(LP, VEC)                                                                                \
-    gsm_attn_aggregate_kernel<LP, VEC><<<blocks, 256, 0, s>>>(q, k, v, edge_w, w_e, row_ptr, col, skip, \
-                                                              n_nodes, HC, C, scale, out, lse)
-    if (vec4) {
-        switch (lp) {
-            case 1: GSM_ATTN(1, 4); break;
-            case 2: GSM_ATTN(2, 4); break;
-            case 4: GSM_ATTN(4, 4); break;
-            case 8: GSM_ATTN(8, 4); break;
-            case 16: GSM_ATTN(16, 4); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (lp) {
-            case 1: GSM_ATTN(1, 1); break;
-            case 2: GSM_ATTN(2, 1); break;
-            case 4: GSM_ATTN(4, 1); break;
-            case 8: GSM_ATTN(8, 1); break;
-            case 16: GSM_ATTN(16, 1); break;
-            case 32: GSM_ATTN(32, 1); break;
-            case 64: GSM_ATTN(64, 1); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef GSM_ATTN
-    return hipGetLastError();
+    const hipError_t e = dispatch_lanes(l, [&](auto LP, auto VEC) {
+        gsm_attn_aggregate_kernel<decltype(LP)::value, decltype(VEC)::value><<<blocks, 256, 0, s>>>(
+            q, k, v, edge_w, w_e, row_ptr, col, skip, n_nodes, HC, C, scale, out, lse);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -347,32 +373,62 @@ __global__ __launch_bounds__(256) void gsm_attn_bwd_target_kernel(
     }
 }
 
-// one block of 64 * kBwdSumRows threads: row group r sums partials r, r+R, ..
-// in order, then channel c's thread sums the R row groups in order
-__global__ __launch_bounds__(64 * kBwdSumRows) void gsm_attn_bwd_dwe_kernel(const float *__restrict__ part,
-                                                                            int n_part, int HC,
-                                                                            float *__restrict__ dw_e) {
+// Where the columns of a summed partial row go: up to four consecutive
+// segments, segment i the columns [end[i-1], end[i]) into ptr[i] (nullptr: not
+// stored); the segments past the last one used are empty.
+struct SumSegments {
+    int end[4];
+    float *ptr[4];
+};
+
+// The sum of n_part partial rows of P floats, for every gradient that
+// workgroups leave as one partial each: a workgroup of 64 * kBwdSumRows
+// threads takes 64 of the columns; row group r sums partials r, r+R, .. in
+// order, then the column's thread sums the R row groups in order.
+__global__ __launch_bounds__(64 * kBwdSumRows) void gsm_partial_sum_kernel(const float *__restrict__ part,
+                                                                           int n_part, int P,
+                                                                           const SumSegments seg) {
     __shared__ float red[kBwdSumRows][64];
-    const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
     float sum = 0.0f;
-    if (c < HC)
+    if (c < P)
         for (int b = r; b < n_part; b += 8 * kBwdSumRows) {
             float x[8];                                    // eight loads in flight, added in order
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int bu = b + u * kBwdSumRows;
-                x[u] = bu < n_part ? part[(int64_t)bu * HC + c] : 0.0f;
+                x[u] = bu < n_part ? part[(int64_t)bu * P + c] : 0.0f;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) sum += x[u];
         }
-    red[r][c] = sum;
+    red[r][lane] = sum;
     __syncthreads();
-    if (r == 0 && c < HC) {
+    if (r == 0 && c < P) {
         float tot = 0.0f;
-        for (int i = 0; i < kBwdSumRows; ++i) tot += red[i][c];
-        dw_e[c] = tot;
+        for (int i = 0; i < kBwdSumRows; ++i) tot += red[i][lane];
+        int lo = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (c >= lo && c < seg.end[i] && seg.ptr[i]) seg.ptr[i][c - lo] = tot;
+            lo = seg.end[i];
+        }
     }
+}
+
+// the partials' sum into the segments given as (length, pointer), in order
+static void launch_partial_sum(const float *part, int n_part,
+                               std::initializer_list<std::pair<int, float *>> segments, hipStream_t s) {
+    SumSegments seg;
+    int P = 0, n = 0;
+    for (const auto &sg : segments) {
+        P += sg.first;
+        seg.end[n] = P;
+        seg.ptr[n++] = sg.second;
+    }
+    for (; n < 4; ++n) seg.end[n] = P, seg.ptr[n] = nullptr;
+    gsm_partial_sum_kernel<<<(unsigned)((P + 63) / 64), 64 * kBwdSumRows, 0, s>>>(part, n_part, P, seg);
 }
 
 template <int kLP, int kVec>
@@ -429,15 +485,9 @@ hipError_t launch_attn_backward(const float *g, const float *q, const float *k, 
                                 const int64_t *t_ptr, const int32_t *t_edge, const int32_t *t_tgt,
                                 int64_t n_nodes, int64_t n_edges, int HC, int C, float scale, float *work,
                                 float *dq, float *dk, float *dv, float *dedge_w, float *dw_e, hipStream_t s) {
-    const bool vec4 =
-        C % 4 == 0 && HC % 4 == 0 &&
-        ((uintptr_t)g | (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dq |
-         (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)(skip ? skip : out) | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
-    const int vec = vec4 ? 4 : 1;
-    int lp = 1;
-    while (lp * vec < HC) lp <<= 1;
-    if (lp > kWave) return hipErrorInvalidValue;
-    const int npw = kWave / lp;
+    const Lanes l = select_lanes(HC, C, aligned16({g, q, k, v, out, dq, dk, dv, skip, w_e}));
+    if (!l.ok) return hipErrorInvalidValue;
+    const int npw = kWave / l.lp;
     const int64_t waves = (n_nodes + npw - 1) / npw;
     const int64_t groups = (waves + 3) / 4;
     const unsigned blocks_a = (unsigned)(groups < kBwdMaxBlocks ? groups : kBwdMaxBlocks);
@@ -445,37 +495,16 @@ hipError_t launch_attn_backward(const float *g, const float *q, const float *k, 
     const int H = HC / C;
     float *wa = work, *wds = work + n_edges * H, *part = dw_e ? work + 2 * n_edges * H : nullptr;
     (void)hipGetLastError();
-#define GSM_ATTN_BWD(LP, VEC)                                                                              \
-    do {                                                                                                   \
-        gsm_attn_bwd_target_kernel<LP, VEC><<<blocks_a, 256, 0, s>>>(g, q, k, v, edge_w, w_e, row_ptr, col, \
-                                                                     out, skip, lse, n_nodes, groups, HC, C, \
-                                                                     scale, wa, wds, part, dq, dedge_w);    \
-        gsm_attn_bwd_source_kernel<LP, VEC><<<blocks_b, 256, 0, s>>>(g, q, wa, wds, t_ptr, t_edge, t_tgt,   \
-                                                                     n_nodes, HC, C, scale, dk, dv);        \
-    } while (0)
-    if (vec4) {
-        switch (lp) {
-            case 1: GSM_ATTN_BWD(1, 4); break;
-            case 2: GSM_ATTN_BWD(2, 4); break;
-            case 4: GSM_ATTN_BWD(4, 4); break;
-            case 8: GSM_ATTN_BWD(8, 4); break;
-            case 16: GSM_ATTN_BWD(16, 4); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (lp) {
-            case 1: GSM_ATTN_BWD(1, 1); break;
-            case 2: GSM_ATTN_BWD(2, 1); break;
-            case 4: GSM_ATTN_BWD(4, 1); break;
-            case 8: GSM_ATTN_BWD(8, 1); break;
-            case 16: GSM_ATTN_BWD(16, 1); break;
-            case 32: GSM_ATTN_BWD(32, 1); break;
-            case 64: GSM_ATTN_BWD(64, 1); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef GSM_ATTN_BWD
-    if (dw_e) gsm_attn_bwd_dwe_kernel<<<1, 64 * kBwdSumRows, 0, s>>>(part, (int)blocks_a, HC, dw_e);
+    const hipError_t e = dispatch_lanes(l, [&](auto LP, auto VEC) {
+        constexpr int kLP = decltype(LP)::value, kVec = decltype(VEC)::value;
+        gsm_attn_bwd_target_kernel<kLP, kVec><<<blocks_a, 256, 0, s>>>(g, q, k, v, edge_w, w_e, row_ptr, col, out,
+                                                                       skip, lse, n_nodes, groups, HC, C, scale, wa,
+                                                                       wds, part, dq, dedge_w);
+        gsm_attn_bwd_source_kernel<kLP, kVec><<<blocks_b, 256, 0, s>>>(g, q, wa, wds, t_ptr, t_edge, t_tgt, n_nodes,
+                                                                       HC, C, scale, dk, dv);
+    });
+    if (e != hipSuccess) return e;
+    if (dw_e) launch_partial_sum(part, (int)blocks_a, {{HC, dw_e}}, s);   // HC <= 64: one workgroup
     return hipGetLastError();
 }
 
@@ -1055,13 +1084,8 @@ hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, cons
                            const float *w_e, int64_t B, int E, int HC, int C, float scale, bool skip,
                            int n_rows_out, float *out, float *lse, int64_t *row_ptr_out, int32_t *status,
                            hipStream_t s) {
-    // four channels per lane when every head spans whole lanes and the rows are 16-byte aligned
-    const bool vec4 = C % 4 == 0 && HC % 4 == 0 &&
-                      ((uintptr_t)out | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
-    const int vec = vec4 ? 4 : 1;
-    int lp = 1;
-    while (lp * vec < HC) lp <<= 1;
-    if (lp > kWave) return hipErrorInvalidValue;
+    const Lanes l = select_lanes(HC, C, aligned16({out, w_e}));
+    if (!l.ok) return hipErrorInvalidValue;
     ConvParams p;
     p.node_feat = node_feat;
     p.edge_ptr = edge_ptr;
@@ -1088,36 +1112,14 @@ hipError_t launch_env_conv(const float *node_feat, const int64_t *edge_ptr, cons
     if (lds > (size_t)kConvLdsMax) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((B + p.epb - 1) / p.epb);
     (void)hipGetLastError();
-#define GSM_CONV(LP, VEC)                                                                                       \
-    do {                                                                                                        \
-        if (table && lse) gsm_env_conv_kernel<LP, VEC, true, true><<<blocks, kConvThreads, lds, s>>>(p);        \
-        else if (table) gsm_env_conv_kernel<LP, VEC, true, false><<<blocks, kConvThreads, lds, s>>>(p);         \
-        else if (lse) gsm_env_conv_kernel<LP, VEC, false, true><<<blocks, kConvThreads, lds, s>>>(p);           \
-        else gsm_env_conv_kernel<LP, VEC, false, false><<<blocks, kConvThreads, lds, s>>>(p);                   \
-    } while (0)
-    if (vec4) {
-        switch (lp) {
-            case 1: GSM_CONV(1, 4); break;
-            case 2: GSM_CONV(2, 4); break;
-            case 4: GSM_CONV(4, 4); break;
-            case 8: GSM_CONV(8, 4); break;
-            case 16: GSM_CONV(16, 4); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (lp) {
-            case 1: GSM_CONV(1, 1); break;
-            case 2: GSM_CONV(2, 1); break;
-            case 4: GSM_CONV(4, 1); break;
-            case 8: GSM_CONV(8, 1); break;
-            case 16: GSM_CONV(16, 1); break;
-            case 32: GSM_CONV(32, 1); break;
-            case 64: GSM_CONV(64, 1); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef GSM_CONV
-    return hipGetLastError();
+    const hipError_t e = dispatch_lanes(l, [&](auto LP, auto VEC) {
+        constexpr int kLP = decltype(LP)::value, kVec = decltype(VEC)::value;
+        if (table && lse) gsm_env_conv_kernel<kLP, kVec, true, true><<<blocks, kConvThreads, lds, s>>>(p);
+        else if (table) gsm_env_conv_kernel<kLP, kVec, true, false><<<blocks, kConvThreads, lds, s>>>(p);
+        else if (lse) gsm_env_conv_kernel<kLP, kVec, false, true><<<blocks, kConvThreads, lds, s>>>(p);
+        else gsm_env_conv_kernel<kLP, kVec, false, false><<<blocks, kConvThreads, lds, s>>>(p);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -1454,38 +1456,6 @@ __global__ __launch_bounds__(kConvThreads, kTable ? 3 : 2) void gsm_env_conv_bwd
     }
 }
 
-// partial sums -> dw, dw_e: a workgroup takes 64 of the values; row group r
-// sums partials r, r+R, .. in order, then the value's thread sums the R row
-// groups in order (gsm_attn_bwd_dwe_kernel's scheme)
-__global__ __launch_bounds__(64 * kBwdSumRows) void gsm_env_conv_bwd_sum_kernel(const float *__restrict__ part,
-                                                                                int n_part, int n_w, int n_e,
-                                                                                float *__restrict__ dw,
-                                                                                float *__restrict__ dw_e) {
-    __shared__ float red[kBwdSumRows][64];
-    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane, W = n_w + n_e;
-    float sum = 0.0f;
-    if (c < W)
-        for (int b = r; b < n_part; b += 8 * kBwdSumRows) {
-            float x[8];                                    // eight loads in flight, added in order
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int bu = b + u * kBwdSumRows;
-                x[u] = bu < n_part ? part[(int64_t)bu * W + c] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += x[u];
-        }
-    red[r][lane] = sum;
-    __syncthreads();
-    if (r == 0 && c < W) {
-        float tot = 0.0f;
-        for (int i = 0; i < kBwdSumRows; ++i) tot += red[i][lane];
-        if (c < n_w) dw[c] = tot;
-        else if (dw_e) dw_e[c - n_w] = tot;
-    }
-}
-
 int64_t env_conv_backward_work_floats(int64_t edge_limit, int heads, int HC, bool skip) {
     return 2 * edge_limit * heads + (int64_t)kConvBwdMaxBlocks * ((skip ? 4 : 3) * HC * 8 + HC);
 }
@@ -1497,12 +1467,8 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
                                     int n_rows_out, float *work, float *dw, float *dw_e, int32_t *status,
                                     hipStream_t s) {
     // the forward's choice of lanes, so that s_ij is formed in the forward's order
-    const bool vec4 = C % 4 == 0 && HC % 4 == 0 &&
-                      ((uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)(w_e ? w_e : out)) % 16 == 0;
-    const int vec = vec4 ? 4 : 1;
-    int lp = 1;
-    while (lp * vec < HC) lp <<= 1;
-    if (lp > kWave) return hipErrorInvalidValue;
+    const Lanes l = select_lanes(HC, C, aligned16({out, grad_out, w_e}));
+    if (!l.ok) return hipErrorInvalidValue;
     const int H = HC / C, nblk = skip ? 4 : 3;
     ConvBwdParams bp;
     ConvParams &p = bp.f;
@@ -1535,7 +1501,7 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
     bp.n_groups = (int)((B + p.epb - 1) / p.epb);
     bp.want_dwe = w_e && dw_e;
     // the table form when it fits with the stage, as launch_env_conv decides it
-    const int stage = conv_bwd_stage_bytes(vec, HC);
+    const int stage = conv_bwd_stage_bytes(l.vec, HC);
     const bool table = conv_lds(p.epb, E, HC, true).total + stage <= kConvLdsMax;
     const size_t lds = (size_t)(conv_lds(p.epb, E, HC, table).total + stage);
     if (lds > (size_t)kConvLdsMax) return hipErrorInvalidValue;
@@ -1543,36 +1509,13 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
     const int cap = min(kConvBwdMaxBlocks, kConvBwdCus * per_cu);
     const unsigned blocks = (unsigned)(bp.n_groups < cap ? bp.n_groups : cap);
     (void)hipGetLastError();
-#define GSM_CONV_BWD(LP, VEC)                                                                     \
-    do {                                                                                          \
-        if (table) gsm_env_conv_bwd_kernel<LP, VEC, true><<<blocks, kConvThreads, lds, s>>>(bp);  \
-        else gsm_env_conv_bwd_kernel<LP, VEC, false><<<blocks, kConvThreads, lds, s>>>(bp);       \
-    } while (0)
-    if (vec4) {
-        switch (lp) {
-            case 1: GSM_CONV_BWD(1, 4); break;
-            case 2: GSM_CONV_BWD(2, 4); break;
-            case 4: GSM_CONV_BWD(4, 4); break;
-            case 8: GSM_CONV_BWD(8, 4); break;
-            case 16: GSM_CONV_BWD(16, 4); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (lp) {
-            case 1: GSM_CONV_BWD(1, 1); break;
-            case 2: GSM_CONV_BWD(2, 1); break;
-            case 4: GSM_CONV_BWD(4, 1); break;
-            case 8: GSM_CONV_BWD(8, 1); break;
-            case 16: GSM_CONV_BWD(16, 1); break;
-            case 32: GSM_CONV_BWD(32, 1); break;
-            case 64: GSM_CONV_BWD(64, 1); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef GSM_CONV_BWD
-    const int n_w = nblk * HC * 8;
-    gsm_env_conv_bwd_sum_kernel<<<(unsigned)((n_w + HC + 63) / 64), 64 * kBwdSumRows, 0, s>>>(
-        bp.part, (int)blocks, n_w, HC, dw, dw_e);
+    const hipError_t e = dispatch_lanes(l, [&](auto LP, auto VEC) {
+        constexpr int kLP = decltype(LP)::value, kVec = decltype(VEC)::value;
+        if (table) gsm_env_conv_bwd_kernel<kLP, kVec, true><<<blocks, kConvThreads, lds, s>>>(bp);
+        else gsm_env_conv_bwd_kernel<kLP, kVec, false><<<blocks, kConvThreads, lds, s>>>(bp);
+    });
+    if (e != hipSuccess) return e;
+    launch_partial_sum(bp.part, (int)blocks, {{nblk * HC * 8, dw}, {HC, dw_e}}, s);   // dw_e may be nullptr
     return hipGetLastError();
 }
 

@@ -10,6 +10,8 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import torch
+
 LIB_PATH = Path(os.environ.get("GSM_LIB_PATH") or Path(__file__).resolve().parent / "lib" / "libgsm.so")
 ABI_VERSION = 8
 DEGENERATE_COINCIDENT, DEGENERATE_NONFINITE = 1, 2
@@ -180,6 +182,24 @@ def last_error(lib, handle=None) -> str:
 def check(lib, rc: int, handle=None, what: str = "") -> None:
     if rc != GSM_OK:
         raise GsmError(f"{what} failed (status {rc}): {last_error(lib, handle)}")
+
+
+def ptr(t):
+    """A tensor's address as a ctypes argument; None (NULL) for no tensor or an empty one, which has no address."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def stream(device):
+    """The raw handle of torch's current stream on ``device`` as a ctypes argument."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def work_floats(query: str, *shape) -> int:
+    """Floats of workspace a kernel wants: ``query`` names one of the ``gsm_*_work_floats`` entry points."""
+    lib = load()
+    nf = C.c_int64()
+    check(lib, getattr(lib, query)(*shape, C.byref(nf)), None, query)
+    return int(nf.value)
 
 
 def make_config(cfg) -> GsmConfig:

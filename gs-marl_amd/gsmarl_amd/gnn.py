@@ -41,7 +41,6 @@ env emits *is* that CSR: ``env_csr`` only adds per-node row offsets.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
@@ -191,8 +190,7 @@ def _check_kernel_inputs(q, k, v, row_ptr, col, edge_w, w_e, what):
         raise ValueError("edge_w: float32, with w_e")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = _lib.ptr
 
 
 class _AttnAggregateFn(torch.autograd.Function):
@@ -207,7 +205,7 @@ class _AttnAggregateFn(torch.autograd.Function):
         # an empty tensor has no address; without edges the kernel reads neither col nor the edge terms
         col_arg = col if col.numel() else col.new_zeros(1)
         ew_arg, we_arg = (edge_w, w_e) if col.numel() else (None, None)
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        stream = _lib.stream(q.device)
         rc = lib.gsm_attn_aggregate_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(ew_arg), _ptr(we_arg), _ptr(row_ptr),
                                         _ptr(col_arg), _ptr(skip), int(n), int(heads), int(HC // heads), scale,
                                         _ptr(out), _ptr(lse), stream)
@@ -227,11 +225,9 @@ class _AttnAggregateFn(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         dedge_w = torch.empty_like(edge_w) if (ctx.needs_input_grad[5] and edge_w is not None) else None
         dw_e = torch.empty_like(w_e) if (ctx.needs_input_grad[6] and w_e is not None) else None
-        nf = C.c_int64()
-        _lib.check(lib, lib.gsm_attn_backward_work_floats(int(n), int(nE), int(heads), int(HC // heads),
-                                                          C.byref(nf)), None, "gsm_attn_backward_work_floats")
-        work = torch.empty(nf.value, dtype=torch.float32, device=q.device)
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        work = torch.empty(_lib.work_floats("gsm_attn_backward_work_floats", int(n), int(nE), int(heads),
+                                            int(HC // heads)), dtype=torch.float32, device=q.device)
+        stream = _lib.stream(q.device)
         ew_arg, we_arg = (edge_w, w_e) if nE else (None, None)
         rc = lib.gsm_attn_aggregate_bwd(_ptr(g), _ptr(q), _ptr(k), _ptr(v), _ptr(ew_arg), _ptr(we_arg), _ptr(row_ptr),
                                         _ptr(col), _ptr(out), _ptr(skip), _ptr(lse), _ptr(t_ptr), _ptr(t_edge),
@@ -285,14 +281,10 @@ def attn_aggregate(q, k, v, row_ptr, col, edge_w=None, w_e=None, skip=None, head
     _check_kernel_inputs(q, k, v, row_ptr, col, edge_w, w_e, "attn_aggregate")
     lib = _lib.load()
     out = torch.empty_like(q)
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.gsm_attn_aggregate(ptr(q), ptr(k), ptr(v), ptr(edge_w), ptr(w_e.contiguous() if w_e is not None else None),
-                                ptr(row_ptr), ptr(col), ptr(skip.contiguous() if skip is not None else None),
-                                int(n), int(heads), int(Cc), scale, ptr(out), stream)
+    rc = lib.gsm_attn_aggregate(_ptr(q), _ptr(k), _ptr(v), _ptr(edge_w),
+                                _ptr(w_e.contiguous() if w_e is not None else None), _ptr(row_ptr), _ptr(col),
+                                _ptr(skip.contiguous() if skip is not None else None), int(n), int(heads), int(Cc),
+                                scale, _ptr(out), _lib.stream(dev))
     _lib.check(lib, rc, None, "gsm_attn_aggregate")
     return out
 
@@ -446,7 +438,7 @@ def env_conv(node_feat, edge_ptr, edge_index, edge_attr, w, w_e, heads, rows_out
     out = torch.empty(B, int(rows_out), HC, dtype=torch.float32, device=dev)
     ptr = torch.empty(B * E + 1, dtype=torch.int64, device=dev) if row_ptr else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _lib.stream(dev)
     rc = lib.gsm_env_conv(_ptr(node_feat) if B else None, _ptr(edge_ptr), _ptr(edge_index) if limit else None, stride,
                           _ptr(edge_attr) if limit else None, limit, _ptr(w), _ptr(w_e), int(B), int(E), int(heads),
                           int(Cc), 1.0 / math.sqrt(Cc), _lib.CONV_SKIP if skip else 0, int(rows_out), _ptr(out),
@@ -475,7 +467,7 @@ class _EnvConvFn(torch.autograd.Function):
         lse = torch.empty(B, rows_out, heads, dtype=torch.float32, device=dev)
         ptr = torch.empty(B * E + 1, dtype=torch.int64, device=dev) if want_ptr else None
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         rc = lib.gsm_env_conv_fwd(_ptr(node_feat) if B else None, _ptr(edge_ptr), _ptr(edge_index) if limit else None,
                                   stride, _ptr(edge_attr) if limit else None, limit, _ptr(w), _ptr(w_e), int(B),
                                   int(E), int(heads), int(Cc), 1.0 / math.sqrt(Cc), _lib.CONV_SKIP if skip else 0,
@@ -500,13 +492,11 @@ class _EnvConvFn(torch.autograd.Function):
         lib = _lib.load()
         g = grad_out.to(torch.float32).contiguous()
         flags = _lib.CONV_SKIP if skip else 0
-        nf = C.c_int64()
-        _lib.check(lib, lib.gsm_env_conv_backward_work_floats(int(B), int(E), limit, int(heads), int(Cc), flags,
-                                                              C.byref(nf)), None, "gsm_env_conv_backward_work_floats")
-        work = torch.empty(nf.value, dtype=torch.float32, device=dev)
+        work = torch.empty(_lib.work_floats("gsm_env_conv_backward_work_floats", int(B), int(E), limit, int(heads),
+                                            int(Cc), flags), dtype=torch.float32, device=dev)
         dw = torch.empty_like(w)
         dw_e = torch.empty_like(w_e) if (w_e is not None and ctx.needs_input_grad[1]) else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         rc = lib.gsm_env_conv_bwd(_ptr(g) if B else None, _ptr(node_feat) if B else None, _ptr(edge_ptr),
                                   _ptr(edge_index) if limit else None, stride, _ptr(edge_attr) if limit else None,
                                   limit, _ptr(w), _ptr(w_e), _ptr(out) if B else None, _ptr(lse) if B else None,

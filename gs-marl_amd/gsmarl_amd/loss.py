@@ -15,12 +15,12 @@ differentiable), the kernel's reference and the fallback;
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
 from . import _lib
-from .policy import _ptr, _stream
+
+_ptr, _stream = _lib.ptr, _lib.stream
 
 N_STATS = 8     # loss, policy term, entropy, value loss of head 0 and 1, approximate KL, clip fraction, W
 
@@ -146,10 +146,7 @@ def ppo_loss_grads_ref(logp, ent, values, logp_old, adv, v_old, ret, weight=None
 
 def ppo_loss_work_floats(n_rows: int) -> int:
     """Floats of workspace ``gsm_ppo_loss`` wants (``gsm_ppo_loss_work_floats``)."""
-    lib = _lib.load()
-    nf = C.c_int64()
-    _lib.check(lib, lib.gsm_ppo_loss_work_floats(int(n_rows), C.byref(nf)), None, "gsm_ppo_loss_work_floats")
-    return int(nf.value)
+    return _lib.work_floats("gsm_ppo_loss_work_floats", int(n_rows))
 
 
 def _ppo_loss_call(logp, ent, values, logp_old, adv, v_old, ret, weight, n_valid, lam, status, coef, grads):

@@ -25,7 +25,6 @@ whose statistics the kernel denormalises with.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -136,12 +135,7 @@ def actor_eval_bwd_ref(g_logp, g_ent, x, w1, b1, w2, b2, actions):
     return dh.t() @ x, dh.sum(0), dw2, db2, dh @ w1
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_ptr, _stream = _lib.ptr, _lib.stream
 
 
 def _rows(x):
@@ -197,10 +191,8 @@ class _ActorEvalFn(torch.autograd.Function):
         hidden, nA = (int(w1.shape[0]) if w1 is not None else 0), int(w2.shape[0])
         g_logp = g_logp.to(torch.float32).contiguous()
         g_ent = g_ent.to(torch.float32).contiguous()
-        nf = C.c_int64()
-        _lib.check(lib, lib.gsm_actor_backward_work_floats(int(F), hidden, nA, C.byref(nf)), None,
-                   "gsm_actor_backward_work_floats")
-        work = torch.empty(nf.value, dtype=torch.float32, device=dev)
+        work = torch.empty(_lib.work_floats("gsm_actor_backward_work_floats", int(F), hidden, nA),
+                           dtype=torch.float32, device=dev)
         dw1 = torch.empty_like(w1) if w1 is not None else None
         db1 = torch.empty_like(b1) if b1 is not None else None
         dw2, db2 = torch.empty_like(w2), torch.empty_like(b2)
@@ -428,11 +420,7 @@ def _critic_eval(x, w1, b1, w2, b2, n_valid, denorm, status):
 
 def critic_work_floats(in_features: int, hidden: int, n_out: int) -> int:
     """Floats of workspace ``gsm_critic_eval_bwd`` wants (``gsm_critic_backward_work_floats``)."""
-    lib = _lib.load()
-    nf = C.c_int64()
-    _lib.check(lib, lib.gsm_critic_backward_work_floats(int(in_features), int(hidden), int(n_out), C.byref(nf)), None,
-               "gsm_critic_backward_work_floats")
-    return int(nf.value)
+    return _lib.work_floats("gsm_critic_backward_work_floats", int(in_features), int(hidden), int(n_out))
 
 
 class _CriticEvalFn(torch.autograd.Function):

@@ -10,7 +10,6 @@ drawing convention is pinned to the demo GIFs (oracle/render_ref.py).
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence
 
 import torch
@@ -43,14 +42,12 @@ def render_frames(node_feat: torch.Tensor, edge_ptr: Optional[torch.Tensor], edg
         flags |= _lib.RENDER_EDGES
         cap = edge_index.shape[1]
 
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
+    ptr = _lib.ptr
     lib = _lib.load()
     rc = lib.gsm_render(ptr(nf), int(nf.shape[0]), int(nf.shape[1]), ptr(edge_ptr) if edges else None,
                         ptr(edge_index) if edges else None, int(cap), ptr(ids), int(n), float(half_width),
                         float(sizes[0]), float(sizes[1]), float(sizes[2]), int(width), int(height), flags,
-                        ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                        ptr(out), _lib.stream(dev))
     _lib.check(lib, rc, None, "gsm_render")
     return out[..., :3]
 

@@ -36,7 +36,6 @@ transposed graph) the attention kernels take, in two HIP launches
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -45,8 +44,7 @@ from . import _lib
 from .batch import GpuBatchEnv
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+_ptr = _lib.ptr
 
 
 class GraphRolloutBuffer:
@@ -232,7 +230,7 @@ class GraphRolloutBuffer:
                         status=torch.zeros(1, dtype=i32, device=dev))
         lib = _lib.load()
         S, B = self.T + 1, self.B
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         # sample offsets [K+1] and the status word in one allocation: its last
         # two words come back in one copy
         head = torch.zeros(K + 2, dtype=i64, device=dev)
@@ -299,7 +297,7 @@ class GraphRolloutBuffer:
             v = values.to(torch.float32).contiguous()
             ret = torch.empty_like(r)
             lib = _lib.load()
-            stream = C.c_void_p(torch.cuda.current_stream(r.device).cuda_stream)
+            stream = _lib.stream(r.device)
             # gamma * gae_lambda: the double product, rounded once to fp32 as the loop's scalar is
             rc = lib.gsm_gae(_ptr(r), _ptr(v), _ptr(self.done), self.T, self.B, self.N, float(gamma),
                              float(gamma * gae_lambda), _ptr(ret), stream)
