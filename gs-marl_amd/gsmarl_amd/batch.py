@@ -283,8 +283,10 @@ class GpuBatchEnv:
         last step's edges are left unemitted — a timing tool) or "roll"
         (all n_steps steps and their edges in ONE fused rollout launch;
         navigation configs with a compiled rollout shape (3, 6, 12 or 24
-        agents with as many obstacles) or the tile path — GsmError otherwise;
-        with time_ends the events bracket that launch).
+        agents with as many obstacles) or the tile path, and every ragged
+        batch (polygon, line, mixed: one env per wave, each step's edges
+        packed `depth` steps later) — GsmError otherwise; with time_ends the
+        events bracket that launch).
         timing: event nodes around every kernel (implies "unfused");
         time_ends: only around the whole graph (per-kernel means over
         back-to-back launches)."""
