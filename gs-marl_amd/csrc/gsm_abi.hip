@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "gsm.h"
+#include <gsm_optim.h>   // include/gsm_optim.h (in quotes it would be the kernels' header beside this file)
 #include "gsm_internal.h"
 #include "gsm_philox.h"
 #include "gsm_roll_plan.h"
@@ -1858,6 +1859,37 @@ int gsm_ppo_loss(const float *logp, const float *ent, const float *values, const
     p.status = status;
     const hipError_t e = gsm::launch_ppo_loss(p, as_stream(stream));
     return launched(e, "gsm_ppo_loss launch");
+}
+
+int gsm_adam_work_floats(int64_t n_tensors, int64_t total_elements, int64_t *n_floats) {
+    if (n_tensors < 0 || total_elements < 0) return fail(nullptr, GSM_EINVAL, "n_tensors and total_elements >= 0");
+    if (!n_floats) return fail(nullptr, GSM_EINVAL, "n_floats is NULL");
+    *n_floats = gsm::adam_work_floats(n_tensors, total_elements);
+    return GSM_OK;
+}
+
+int gsm_adam_step(float *const *p, const float *const *g, float *const *m, float *const *v, const int64_t *n,
+                  int64_t n_tensors, const float *lr, int32_t *step, double beta1, double beta2, double eps,
+                  float max_norm, float *work, float *stats, int32_t *status, void *stream) {
+    static_assert(GSM_OPT_NONFINITE == gsm::kOptNonfinite, "the status bit of gsm_optim.h");
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_tensors < 0) return fail(nullptr, GSM_EINVAL, "n_tensors must be >= 0");
+    if (n_tensors > 0 && (!p || !g || !m || !v || !n)) return fail(nullptr, GSM_EINVAL, "a tensor array is NULL");
+    for (int64_t i = 0; i < n_tensors; ++i) {
+        if (n[i] < 0 || n[i] >= lim) return fail(nullptr, GSM_EINVAL, "every n[i] must be in [0, 2^31)");
+        if (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i]))
+            return fail(nullptr, GSM_EINVAL, "a pointer of a tensor with elements is NULL");
+    }
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0))
+        return fail(nullptr, GSM_EINVAL, "beta1 and beta2 must be in [0, 1)");
+    if (!(eps >= 0.0) || !(max_norm >= 0.0f)) return fail(nullptr, GSM_EINVAL, "eps and max_norm must be >= 0");
+    if (!lr || !step || !work || !stats) return fail(nullptr, GSM_EINVAL, "lr, step, work or stats is NULL");
+    if ((uintptr_t)work % 8) return fail(nullptr, GSM_EINVAL, "work must be 8-byte aligned");
+    gsm::OptScalars sc = {};
+    sc.beta1 = beta1, sc.beta2 = beta2, sc.eps = eps, sc.max_norm = max_norm;
+    const hipError_t e = gsm::launch_adam_step(p, g, m, v, n, n_tensors, sc, lr, step, work, stats, status,
+                                               as_stream(stream));
+    return launched(e, "gsm_adam_step launch");
 }
 
 int gsm_gae(const float *reward, const float *value, const uint8_t *done, int64_t n_steps, int64_t n_envs,

@@ -26,6 +26,7 @@
 #include <initializer_list>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "gsm.h"
 #include "gsm_device.h"
@@ -1527,3 +1528,5 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
 #include "gsm_critic.h"
 // the PPO / Lagrangian loss: gsm_ppo_loss
 #include "gsm_loss.h"
+// the optimizer step: gsm_adam_step
+#include "gsm_optim.h"

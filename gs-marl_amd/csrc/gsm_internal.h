@@ -373,6 +373,32 @@ struct LossParams {
 // floats of workspace launch_ppo_loss needs: one [8] partial per workgroup of its capped grid
 int64_t ppo_loss_work_floats();
 hipError_t launch_ppo_loss(const LossParams &p, hipStream_t s);
+// the optimizer step (gsm_optim.h): one launch's table of tensors, by value in
+// the kernel arguments (1560 bytes). first_chunk: the tensor's first chunk in
+// the numbering of the whole call; [chunk_lo, chunk_hi) the launch's chunks
+constexpr int kOptTable = 32;
+constexpr int kOptNonfinite = 1;         // GSM_OPT_NONFINITE
+struct OptTensor {
+    float *p;
+    const float *g;
+    float *m, *v;
+    int64_t n, first_chunk;
+};
+struct OptTable {
+    OptTensor t[kOptTable];
+    int64_t chunk_lo, chunk_hi;
+    int n_tensors;
+};
+struct OptScalars {
+    double beta1, beta2, eps;
+    float max_norm;
+};
+// floats of workspace launch_adam_step needs: a header and one fp64 partial per chunk
+int64_t adam_work_floats(int64_t n_tensors, int64_t total_elements);
+// p, g, m, v, n: host arrays of n_tensors entries; work 8-byte aligned
+hipError_t launch_adam_step(float *const *p, const float *const *g, float *const *m, float *const *v,
+                            const int64_t *n, int64_t n_tensors, const OptScalars &sc, const float *lr,
+                            int32_t *step, float *work, float *stats, int32_t *status, hipStream_t s);
 hipError_t launch_gae(const float *reward, const float *value, const uint8_t *done, int64_t T, int64_t B, int N,
                       float gamma, float gamma_lambda, float *ret, hipStream_t s);
 hipError_t launch_render(const float *node_feat, int64_t n_envs, int32_t n_entities, const int64_t *edge_ptr,

@@ -11,6 +11,8 @@ from . import policy
 from .policy import ActorHead, CriticHead, PopArt
 from . import loss
 from .loss import LagrangeMultiplier, PPOLagrangianLoss
+from . import optim
+from .optim import ClippedAdam
 from . import render
 from . import distributed
 
@@ -18,4 +20,4 @@ __version__ = "0.1.0"
 __all__ = ["EnvConfig", "GpuBatchEnv", "MultiAgentEnv", "MultiAgentConstrainEnv",
            "MultiAgentGraphConstrainEnv", "make_env", "GpuGraphVecEnv", "make_train_env", "make_eval_env",
            "GraphRolloutBuffer", "gnn", "policy", "ActorHead", "CriticHead", "PopArt", "loss",
-           "PPOLagrangianLoss", "LagrangeMultiplier", "render", "distributed"]
+           "PPOLagrangianLoss", "LagrangeMultiplier", "optim", "ClippedAdam", "render", "distributed"]

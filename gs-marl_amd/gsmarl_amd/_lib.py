@@ -28,6 +28,7 @@ ACTOR_DETERMINISTIC = 1
 ACTOR_NONFINITE, ACTOR_BAD_ACTION = 1, 2
 CRITIC_NONFINITE, CRITIC_BAD_COUNT = 1, 2
 LOSS_NONFINITE, LOSS_BAD_COUNT, LOSS_BAD_WEIGHT = 1, 2, 4
+OPT_NONFINITE = 1
 
 
 class GsmConfig(C.Structure):
@@ -145,6 +146,12 @@ SIGNATURES = {
     "gsm_destroy": (C.c_int, [_P]),
     "gsm_last_error": (C.c_int, [_P, C.c_char_p, C.c_size_t]),
 }
+# every symbol include/gsm_optim.h declares (a header of its own: ABI_VERSION does not count them)
+OPTIM_SIGNATURES = {
+    "gsm_adam_work_floats": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "gsm_adam_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_double,
+                                C.c_float, _P, _P, _P, _P]),
+}
 
 _lib = None
 
@@ -162,7 +169,7 @@ def load(path: os.PathLike | None = None):
     if not p.exists():
         raise GsmError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = C.CDLL(str(p))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
