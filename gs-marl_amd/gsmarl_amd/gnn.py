@@ -607,7 +607,10 @@ class TransformerConv(torch.nn.Module):
 
     def _packed(self):
         """``pack_conv_params`` of the current parameter values, packed again
-        only after a parameter changed (inference path, no gradient)."""
+        only after a parameter changed (inference path, no gradient): the key
+        is every parameter's storage address and ``_version``. A write torch
+        does not see (a kernel writing through ``data_ptr()``) has to raise
+        the version, as ``ClippedAdam.mark_updated`` does."""
         key = tuple((p.data_ptr(), p._version) for p in self.parameters())
         if getattr(self, "_pack_key", None) != key:
             with torch.no_grad():

@@ -91,13 +91,21 @@ def _max_norm(max_grad_norm) -> float:
     return math.inf if max_grad_norm is None else float(max_grad_norm)
 
 
+def _table_key(params):
+    """What a cached ``_Table`` is valid for: the parameters' storage addresses
+    (``p.data = ...`` and ``module.to(...)`` give a parameter another one)."""
+    return tuple(map(torch.Tensor.data_ptr, params))
+
+
 class _Table:
-    """The host arrays of one gsm_adam_step call: p, g, m, v pointers and counts."""
+    """The host arrays of one gsm_adam_step call: p, g, m, v pointers and counts;
+    ``key`` = ``_table_key`` of the parameters it was built from."""
 
     def __init__(self, params, exp_avg, exp_avg_sq):
         k = len(params)
         arr = C.c_void_p * k
         self.k = k
+        self.key = _table_key(params)
         self.p = arr(*(t.data_ptr() if t.numel() else None for t in params))
         self.m = arr(*(t.data_ptr() if t.numel() else None for t in exp_avg))
         self.v = arr(*(t.data_ptr() if t.numel() else None for t in exp_avg_sq))
@@ -150,7 +158,23 @@ class ClippedAdam:
     since it was last zeroed. None of them is read here, and moments, workspace
     and ``stats`` are allocated at construction, so a ``step()`` can be
     captured into a ``torch.cuda.graph`` (with gradients that are rewritten in
-    place) and replayed, interleaved with eager calls."""
+    place) and replayed, interleaved with eager calls.
+
+    The kernel writes the parameters through raw pointers, which torch does not
+    see, so the kernel path of ``step()`` ends with ``mark_updated()``: it
+    raises ``_version`` of every parameter of the last active set (host only:
+    no launch, no synchronisation), as ``copy_`` does on the fallback path.
+    Caches keyed on the version (``TransformerConv._packed``) then repack, and a
+    backward through a graph built before the step raises as it does after
+    ``torch.optim.Adam.step``. A skipped step raises the versions too. A
+    replayed captured step runs no Python: the route is ``graph.replay();
+    opt.mark_updated()``.
+
+    ``step()`` looks at the parameters again on every call, as ``torch.optim``
+    does: after ``p.data = ...`` (or a ``module.to(...)`` that moved nothing off
+    the device) the next eager step updates the new storage. A captured step
+    cannot follow a replaced storage: the graph holds the addresses it was
+    recorded with, so capture again after replacing one."""
 
     def __init__(self, params, lr: float = 7e-4, betas=(0.9, 0.999), eps: float = 1e-5, max_grad_norm=10.0,
                  use_kernel: bool = True):
@@ -176,22 +200,44 @@ class ClippedAdam:
         self.stats = torch.zeros(N_STATS, dtype=torch.float32 if self.kernel else self.params[0].dtype, device=dev)
         self.status = self._work = None
         self._tables = {}
+        self._last, self._marked = (), []            # the active set of the last step() and its parameters
         if self.kernel:
             self.status = torch.zeros(1, dtype=torch.int32, device=dev)
             self._work = torch.empty(adam_work_floats(len(self.params), sum(p.numel() for p in self.params)),
                                      dtype=torch.float32, device=dev)
 
-    def _active(self):
-        return tuple(i for i, p in enumerate(self.params) if p.grad is not None)
+    def _table(self, act, ps, ms, vs):
+        """The cached host arrays of the active set ``act``, built again when a
+        parameter's storage is no longer the one they name."""
+        tab = self._tables.get(act)
+        if tab is None or tab.key != _table_key(ps):
+            if tab is not None and not all(p.device == self.lr.device and p.dtype == torch.float32 and
+                                           p.is_contiguous() and p.shape == m.shape for p, m in zip(ps, ms)):
+                raise ValueError("a parameter's new storage is not a contiguous fp32 tensor of the old shape on the "
+                                 "optimizer's device")
+            tab = self._tables[act] = _Table(ps, ms, vs)
+        return tab
+
+    def mark_updated(self):
+        """Tell torch that the parameters of the last active set were written
+        (``torch.autograd.graph.increment_version``; host only). ``step()``
+        calls it on the kernel path; call it after replaying a captured step."""
+        if self._marked:
+            torch.autograd.graph.increment_version(self._marked)         # one call for the whole list
 
     @torch.no_grad()
     def step(self):
-        act = self._active()
-        ps = [self.params[i] for i in act]
-        ms, vs = [self.exp_avg[i] for i in act], [self.exp_avg_sq[i] for i in act]
-        gs = [p.grad for p in ps]
-        if not ps:                                   # nothing has a gradient: not an update
+        gs = [p.grad for p in self.params]           # .grad is read once a parameter: the host's time is the call's
+        act = tuple(i for i, g in enumerate(gs) if g is not None)
+        if not act:                                  # nothing has a gradient: not an update
             return
+        if len(act) == len(gs):
+            ps, ms, vs = self.params, self.exp_avg, self.exp_avg_sq
+        else:
+            ps, gs = [self.params[i] for i in act], [gs[i] for i in act]
+            ms, vs = [self.exp_avg[i] for i in act], [self.exp_avg_sq[i] for i in act]
+        if act != self._last:
+            self._last, self._marked = act, list(ps)
         if not self.kernel:
             new_p, new_m, new_v, new_step, stats = clipped_adam_ref(ps, gs, ms, vs, self.step_count, self.lr,
                                                                     self.betas, self.eps, self.max_grad_norm)
@@ -200,15 +246,14 @@ class ClippedAdam:
             self.step_count.copy_(new_step)
             self.stats.copy_(stats)
             return
+        dev = self.lr.device                         # every parameter's: by construction, and by _table after p.data = ...
         for p, g in zip(ps, gs):
-            if g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape:
+            if g.dtype != torch.float32 or g.device != dev or g.shape != p.shape:
                 raise ValueError("a gradient is not an fp32 tensor of its parameter's shape and device")
         gs = [g if g.is_contiguous() else g.contiguous() for g in gs]
-        tab = self._tables.get(act)
-        if tab is None:
-            tab = self._tables[act] = _Table(ps, ms, vs)
         _adam_call(ps, gs, ms, vs, self.lr, self.step_count, self.betas, self.eps, self.max_grad_norm, self.status,
-                   self._work, self.stats, tab)
+                   self._work, self.stats, self._table(act, ps, ms, vs))
+        self.mark_updated()
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:

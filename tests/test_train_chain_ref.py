@@ -67,6 +67,48 @@ def test_share_conditions_of_the_committed_seeds(kind):
     assert clipped >= 1
 
 
+@pytest.mark.parametrize("kind", list(tc.SEEDS_W2))
+def test_share_conditions_of_the_second_window_seeds(kind):
+    """The second window of test_gpu_train_iterations.py, as far as the CPU has
+    it: oracle graphs of 2 T steps, the fp32 torch chain, one clipped_adam_ref
+    step (ClippedAdam's defaults) on the first window's gradients with the
+    current actor's own logp_old, then the second window's data with
+    SEEDS_W2[kind]: the fp64 copy of the stepped chain alone decides."""
+    from gsmarl_amd.optim import clipped_adam_ref
+    n_agents, n_envs, form = GPU_CASES[kind]
+    seed = tc.SEEDS[kind]
+    slots, rew, cost, done = tc.oracle_graph(n_envs, n_agents, 2 * T, seed, episode_length=T // 2)
+    E = slots[0]["node_feat"].shape[1]
+    assert bool(done[T - 1].all()) and bool(done[T:2 * T - 1].any())     # on the seam and inside the second window
+    mods = tc.build(kind, 1 if form == "env1" else 2, torch.float32, False)
+    windows = []
+    for lo in (0, T):
+        graph = tc.env_graph(slots[lo:lo + T + 1], n_agents, E, T)
+        gae = {"reward": tc.gae_ref(rew[lo:lo + T], done[lo:lo + T]), "cost": tc.gae_ref(cost[lo:lo + T], done[lo:lo + T])}
+        windows.append((graph, gae))
+    graph, gae = windows[0]
+    data = tc.rollout_data(mods, graph, form, gae, seed, perturb=0.0)
+    grads, out = tc.run(mods, graph, form, data, tc.base_weight(data["logp_old"][..., None]))
+    assert bool((out["ratio"] == 1.0).all())
+    names = list(tc.named_params(mods))
+    params = [tc.named_params(mods)[n] for n in names]
+    zeros = [torch.zeros_like(p) for p in params]
+    new_p, _, _, _, stats = clipped_adam_ref(params, [grads[n] for n in names], zeros, zeros, 0, 7e-4)
+    assert float(stats[3]) == 0.0
+    with torch.no_grad():
+        for p, q in zip(params, new_p):
+            assert not torch.equal(p, q)
+            p.copy_(q)
+    graph, gae = windows[1]
+    data = tc.rollout_data(mods, graph, form, gae, tc.SEEDS_W2[kind])
+    und, outside, clipped = tc.decide(tc.copy_of(mods, torch.float64, False), graph, form, data)[1:]
+    print(f"{kind}, second window: undecided {und:.4%}, outside the clip range {outside:.2%}, clipped value rows "
+          f"{clipped}")
+    assert und <= 0.01
+    assert outside >= 0.10
+    assert clipped >= 1
+
+
 @pytest.mark.parametrize("form", ["env1", "env2"])
 def test_row_scales_add_up_to_the_full_gradient(form):
     s = _setup(form, 6, 16, form)

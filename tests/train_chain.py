@@ -27,6 +27,9 @@ MODULES = ("conv", "conv2", "actor", "critic")
 # one seed per case: the modules, the old actor's perturbation and the draws. test_train_chain_ref.py holds
 # every seed to the share conditions (undecided rows, rows outside the clip range, a clipped value row)
 SEEDS = {"env1": 11, "env2": 12, "n3": 21, "n6-env2": 22, "n6-csr2": 23, "n24": 24, "mixed": 25}
+# the second window of the two-iteration tests (test_gpu_train_iterations.py): the seed of its old actor's
+# perturbation and draws, after one optimizer step; held to the same share conditions
+SEEDS_W2 = {"n3": 31}
 
 
 def _make(layers, dtype, kernel, device):
@@ -390,12 +393,14 @@ def row_scales(ref_mods, graph, data, weight, with_sum=False):
     return (scale, dict(zip(names, tot))) if with_sum else scale
 
 
-def oracle_graph(n_envs, n_agents, n_steps, seed):
+def oracle_graph(n_envs, n_agents, n_steps, seed, episode_length=None):
     """CPU graphs from ``oracle.batch_ref``: a reset and ``n_steps`` steps with
-    random actions, fp32 node features and distances. Returns (slots, reward
-    [T, B, N], cost [T, B, N], done [T, B])."""
+    random actions, fp32 node features and distances; an episode lasts
+    ``episode_length`` steps (half of ``n_steps`` when None). Returns (slots,
+    reward [T, B, N], cost [T, B, N], done [T, B])."""
     from oracle import batch_ref as br
-    cfg = br.make_cfg(n_envs=n_envs, n_agents=n_agents, seed=seed, episode_length=max(n_steps // 2, 1))
+    cfg = br.make_cfg(n_envs=n_envs, n_agents=n_agents, seed=seed,
+                      episode_length=episode_length or max(n_steps // 2, 1))
     st = br.new_state(cfg, seed=seed, dtype=np.float32)
     rng = np.random.default_rng(seed)
 
