@@ -1,5 +1,5 @@
-// gsm_actor.h — the actor head (included by gsm_gnn.hip): features -> MLP ->
-// categorical distribution -> Philox-sampled action, log-probability, entropy
+// gsm_actor.hip — the actor head: features -> MLP -> categorical
+// distribution -> Philox-sampled action, log-probability, entropy
 // (gsm_actor_sample), the same head on stored actions (gsm_actor_eval) and its
 // gradients (gsm_actor_eval_bwd). The contract is in include/gsm.h.
 //
@@ -22,20 +22,17 @@
 // [h | 1] and dW1|db1 = dh^T [x | 1], from LDS with a 4x4 register tile per
 // thread, each tile's products added by their owning thread to the workgroup's
 // partial in `work` (a few KB that stay in L2, so no accumulator is held over
-// the per-row part); gsm_partial_sum_kernel adds the partials in a fixed
-// order. No float atomics. The MLP pieces are gsm_mlp.h's, shared with the
-// critic head.
-#pragma once
+// the per-row part); gsm_partial_sum_kernel (gsm_gnn.hip) adds the partials in
+// a fixed order. No float atomics. The MLP pieces are gsm_mlp.h's, shared with
+// the critic head.
 #include "gsm_mlp.h"
 #include "gsm_philox.h"
 
 namespace gsm {
 
-constexpr int kActorThreads = kMlpThreads;
 constexpr int kActorMaxActions = 8;
 constexpr int kActorFwdMaxBlocks = 2048;
 constexpr int kActorBwdMaxBlocks = 512;  // two per CU: the size of `work`
-constexpr int kActorLdsMax = 160 * 1024;
 
 // LDS, in floats; every block starts on a 16-byte boundary (in % 4 == 0, kH % 16 == 0)
 struct ActorLds {

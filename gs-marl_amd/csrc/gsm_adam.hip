@@ -1,7 +1,6 @@
-// gsm_optim.h — the optimizer step (included by gsm_gnn.hip after gsm_loss.h):
-// the global gradient norm of a list of tensors, the clip coefficient and one
-// Adam update of every tensor in two passes (gsm_adam_step). The contract is in
-// include/gsm_optim.h.
+// gsm_adam.hip — the optimizer step: the global gradient norm of a list of
+// tensors, the clip coefficient and one Adam update of every tensor in two
+// passes (gsm_adam_step). The contract is in include/gsm_optim.h.
 //
 // Mapping: a chunk is kOptChunk = 1024 consecutive elements of one tensor, an
 // item four consecutive elements, one item per thread, 256 threads a workgroup,
@@ -29,8 +28,9 @@
 // from the header's step count), then updates its chunks of p, m, v. Workgroup 0
 // of the call's first launch writes stats, the status and the step word: no
 // workgroup of pass 2 reads the step word. No float atomics.
-#pragma once
-#include "gsm_loss.h"
+#include <vector>
+
+#include "gsm_internal.h"
 
 namespace gsm {
 

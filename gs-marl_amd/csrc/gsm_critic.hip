@@ -1,12 +1,12 @@
-// gsm_critic.h — the critic head (included by gsm_gnn.hip after gsm_actor.h):
-// features -> mean over an env's valid agents -> MLP on [pool | x] -> one or
-// two values a row (gsm_critic_eval) and their gradients (gsm_critic_eval_bwd).
+// gsm_critic.hip — the critic head: features -> mean over an env's valid
+// agents -> MLP on [pool | x] -> one or two values a row (gsm_critic_eval) and
+// their gradients (gsm_critic_eval_bwd).
 // The contract is in include/gsm.h.
 //
 // Mapping: a workgroup of 128 threads takes tiles of whole envs, ept =
 // min(128 / n_agents, 64) envs and ept * n_agents <= 128 rows, one row per
 // thread (thread t: env t / n_agents of the tile, agent t % n_agents). As in
-// gsm_actor.h the weights sit in LDS for the workgroup's life, W1 transposed to
+// gsm_actor.hip the weights sit in LDS for the workgroup's life, W1 transposed to
 // [2 in][hidden] (16-byte broadcast reads that feed four chains), and a tile's
 // x rows are staged by coalesced 16-byte loads, a row padded by (1, 0, 0, 0);
 // padded agents (i >= n_valid[b]) and the rows past the tile's envs are staged
@@ -28,8 +28,7 @@
 // dpool_b = W1[:, :in]^T s_b, whose quotient by n_b every row of the env adds
 // to its dx. gsm_partial_sum_kernel adds the partials in a fixed order. No
 // float atomics. The MLP pieces are gsm_mlp.h's, shared with the actor head.
-#pragma once
-#include "gsm_actor.h"
+#include "gsm_mlp.h"
 
 namespace gsm {
 

@@ -374,14 +374,6 @@ __global__ __launch_bounds__(256) void gsm_attn_bwd_target_kernel(
     }
 }
 
-// Where the columns of a summed partial row go: up to four consecutive
-// segments, segment i the columns [end[i-1], end[i]) into ptr[i] (nullptr: not
-// stored); the segments past the last one used are empty.
-struct SumSegments {
-    int end[4];
-    float *ptr[4];
-};
-
 // The sum of n_part partial rows of P floats, for every gradient that
 // workgroups leave as one partial each: a workgroup of 64 * kBwdSumRows
 // threads takes 64 of the columns; row group r sums partials r, r+R, .. in
@@ -419,8 +411,8 @@ __global__ __launch_bounds__(64 * kBwdSumRows) void gsm_partial_sum_kernel(const
 }
 
 // the partials' sum into the segments given as (length, pointer), in order
-static void launch_partial_sum(const float *part, int n_part,
-                               std::initializer_list<std::pair<int, float *>> segments, hipStream_t s) {
+void launch_partial_sum(const float *part, int n_part, std::initializer_list<std::pair<int, float *>> segments,
+                        hipStream_t s) {
     SumSegments seg;
     int P = 0, n = 0;
     for (const auto &sg : segments) {
@@ -1521,12 +1513,3 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
 }
 
 }  // namespace gsm
-
-// the actor head: gsm_actor_sample / gsm_actor_eval / gsm_actor_eval_bwd
-#include "gsm_actor.h"
-// the critic head: gsm_critic_eval / gsm_critic_eval_bwd
-#include "gsm_critic.h"
-// the PPO / Lagrangian loss: gsm_ppo_loss
-#include "gsm_loss.h"
-// the optimizer step: gsm_adam_step
-#include "gsm_optim.h"

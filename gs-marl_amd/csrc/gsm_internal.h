@@ -1,8 +1,12 @@
-// Internal (non-ABI) declarations shared by gsm_kernels.hip and gsm_abi.hip.
+// Internal (non-ABI) declarations shared by the kernel sources and the C
+// boundary (gsm_abi.hip, gsm_ops.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <initializer_list>
+#include <utility>
 
 namespace gsm {
 
@@ -130,7 +134,7 @@ struct DevParams {
         int32_t *slab;        // ragged rollout: [depth + 1][B] slabs of [slab_e + 1] u32 row-pair words + [slab_e + 1] f32
         const int32_t *place; // ragged rollout: [W] envs by descending cost (nullptr: env = wave index)
         int32_t place_S;      // SIMDs the grid fills (place_R * place_S = W)
-        // pacing of the one-env-per-wave segmented rollout (gsm_seg_kernels.hip
+        // pacing of the one-env-per-wave segmented rollout (gsm_device.h
         // pace_level): the rank offset between a CU's workgroups in quarter
         // steps, and per-CU {workgroups arrived, steps finished} counters
         // [kPaceKeys] of this launch and of the slot's next (zeroed by this
@@ -311,7 +315,19 @@ hipError_t launch_env_conv_backward(const float *grad_out, const float *node_fea
                                     const float *lse, int64_t B, int E, int HC, int C, float scale, bool skip,
                                     int n_rows_out, float *work, float *dw, float *dw_e, int32_t *status,
                                     hipStream_t s);
-// the actor head (gsm_actor.h): what its three launchers take. R = n_envs *
+// Where the columns of a summed partial row go: up to four consecutive
+// segments, segment i the columns [end[i-1], end[i]) into ptr[i] (nullptr: not
+// stored); the segments past the last one used are empty.
+struct SumSegments {
+    int end[4];
+    float *ptr[4];
+};
+// the partials' sum into the segments given as (length, pointer), in order
+// (gsm_gnn.hip gsm_partial_sum_kernel: every gradient that workgroups leave as
+// one partial each)
+void launch_partial_sum(const float *part, int n_part, std::initializer_list<std::pair<int, float *>> segments,
+                        hipStream_t s);
+// the actor head (gsm_actor.hip): what its three launchers take. R = n_envs *
 // n_agents rows; k0, k1 the seed's halves; the forward reads actions_in (eval)
 // or writes actions_out (sample); part: the backward's partials in `work`
 struct ActorParams {
@@ -336,7 +352,7 @@ hipError_t launch_actor_forward(const ActorParams &p, int hidden, bool eval, hip
 int64_t actor_backward_work_floats(int in, int hidden, int nA);
 hipError_t launch_actor_backward(const ActorParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
                                  hipStream_t s);
-// the critic head (gsm_critic.h): what its two launchers take. R = n_envs *
+// the critic head (gsm_critic.hip): what its two launchers take. R = n_envs *
 // n_agents rows; the forward writes values, the backward reads g and writes dx
 // and its partials (part, in `work`)
 struct CriticParams {
@@ -357,7 +373,7 @@ hipError_t launch_critic_forward(const CriticParams &p, int hidden, hipStream_t 
 int64_t critic_backward_work_floats(int in, int hidden, int nO);
 hipError_t launch_critic_backward(const CriticParams &p, int hidden, float *dw1, float *db1, float *dw2, float *db2,
                                   hipStream_t s);
-// the PPO / Lagrangian loss (gsm_loss.h): what its launcher takes. R = n_envs *
+// the PPO / Lagrangian loss (gsm_loss.hip): what its launcher takes. R = n_envs *
 // n_agents rows; values, adv, v_old, ret and g_values head-major [nO][R]; lam
 // the device multiplier; ratio_lo / ratio_hi = 1 -/+ clip rounded once
 struct LossParams {
@@ -373,7 +389,7 @@ struct LossParams {
 // floats of workspace launch_ppo_loss needs: one [8] partial per workgroup of its capped grid
 int64_t ppo_loss_work_floats();
 hipError_t launch_ppo_loss(const LossParams &p, hipStream_t s);
-// the optimizer step (gsm_optim.h): one launch's table of tensors, by value in
+// the optimizer step (gsm_adam.hip): one launch's table of tensors, by value in
 // the kernel arguments (1560 bytes). first_chunk: the tensor's first chunk in
 // the numbering of the whole call; [chunk_lo, chunk_hi) the launch's chunks
 constexpr int kOptTable = 32;

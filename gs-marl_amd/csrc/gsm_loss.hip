@@ -1,7 +1,6 @@
-// gsm_loss.h — the clipped PPO / Lagrangian loss (included by gsm_gnn.hip after
-// gsm_critic.h): logp, entropy and the twin values of the heads -> the loss,
-// eight statistics and the row gradients (gsm_ppo_loss). The contract is in
-// include/gsm.h.
+// gsm_loss.hip — the clipped PPO / Lagrangian loss: logp, entropy and the twin
+// values of the heads -> the loss, eight statistics and the row gradients
+// (gsm_ppo_loss). The contract is in include/gsm.h.
 //
 // Mapping: an item is four consecutive rows, one item per thread, 256 threads a
 // workgroup, a capped grid with a grid-stride loop over the items. With R % 4
@@ -20,8 +19,8 @@
 // same bits) and multiplies its rows' w_r * d_r by 1.0f / W in place;
 // workgroup 0 also adds the other seven partials and writes loss and stats.
 // Without gradients pass 2 is one workgroup. No float atomics.
-#pragma once
-#include "gsm_actor.h"
+#include "gsm.h"
+#include "gsm_internal.h"
 
 namespace gsm {
 

@@ -1,4 +1,4 @@
-// gsm_mlp.h — the device pieces the MLP heads share (gsm_actor.h, gsm_critic.h):
+// gsm_mlp.h — the device pieces the MLP heads share (gsm_actor.hip, gsm_critic.hip):
 // a workgroup of kMlpThreads threads, one row of a tile per thread, the weights
 // in LDS with W1 transposed to [cols][kH], a row's hidden units in registers.
 //
@@ -14,6 +14,9 @@
 namespace gsm {
 
 constexpr int kMlpThreads = 128;   // = rows of a tile
+// both heads' names for the workgroup size and their dynamic-LDS ceiling (the actor head had them first)
+constexpr int kActorThreads = kMlpThreads;
+constexpr int kActorLdsMax = 160 * 1024;
 
 // The weights into LDS (scalar loads: no alignment asked of them). W1
 // [kH][cols] is transposed to [cols][kH]; W2 [n_out][KW] and b2 are padded with

@@ -6,6 +6,7 @@
 // scenario.reset_world): counter = (entity, episode, global env id, TAG),
 // key = (seed lo32, seed hi32); u = (x >> 8) * 2^-24 in [0,1).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #ifndef GSM_HD

@@ -14,7 +14,7 @@ import torch
 
 from gsmarl_amd.optim import clipped_adam_ref
 
-CHUNK, CAP, TABLE = 1024, 1024, 32           # kOptChunk, kOptMaxBlocks (gsm_optim.h), kOptTable (gsm_internal.h)
+CHUNK, CAP, TABLE = 1024, 1024, 32           # kOptChunk, kOptMaxBlocks (gsm_adam.hip), kOptTable (gsm_internal.h)
 SIZES = [1, 5, 63, 64, 65, 255, 256, 257, 1023, 1025, 6144, 336, 2304]
 LOOP = CHUNK * CAP + 1025                    # 1026 chunks
 MANY = [SIZES[i % len(SIZES)] for i in range(TABLE + 8)]
